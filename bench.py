@@ -875,6 +875,22 @@ def roofline_bound(pmc, frac, k):
     return out
 
 
+def dump_outputs(out_dir, res):
+    """--dump-outputs: what a caller of the timed path (ntk_reduce_device, then ntk_accum_read) receives after the last timed step, as
+    float64 arrays that are exact: hist.npy = the 4096 prefix-histogram bins; counts.npy = [n_total, n_fwd, n_rc] (all far below 2^53);
+    digests.npy = the 64-bit sum and xor digests, one row each, split into four 16-bit words, most significant first."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    words16 = lambda v: [(int(v) >> s) & 0xFFFF for s in (48, 32, 16, 0)]
+    arrays = {
+        "hist": np.asarray(res["hist"], dtype=np.float64),
+        "counts": np.array([res["n_total"], res["n_fwd"], res["n_rc"]], dtype=np.float64),
+        "digests": np.array([words16(res["sum"]), words16(res["xor"])], dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -921,7 +937,11 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="do not collect roofline.traffic with rocprofv3 --pmc child passes (N = 1)")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass (profiles/), if known")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the reduced result of the last timed step to DIR/{hist,counts,digests}.npy (float64, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         if not args.single_device:
@@ -1128,6 +1148,8 @@ def main():
         elapsed, kern_avg_ms = float(t[0]), float(t[1])
 
     res = ctx.accum_read() if comm is not None or not use_dist else nd.decode_accumulators(acc)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     if not (res["n_total"] == res["n_fwd"] + res["n_rc"] == int(np.asarray(res["hist"]).sum())
             and 0 < res["n_total"] <= total_reads * (args.read_len - args.k + 1)):
         raise SystemExit(f"inconsistent reduced result: {res['n_total']} {res['n_fwd']} {res['n_rc']}")

@@ -159,3 +159,26 @@ print(json.dumps({{"n_total": st["n_total"], "n_fwd": st["n_fwd"], "sum": st["su
     assert note.startswith("absent (") and "cargo" in note   # this image has no cargo: the C port is the baseline, and the line says why
     eff, info = bench.effective_cpus()
     assert 1 <= eff <= (os.cpu_count() or 1) and info["logical_cpus"] == os.cpu_count()
+
+
+def test_bench_dump_outputs_round_trip(tmp_path):
+    """bench.py --dump-outputs: the reduced result goes out as float64 .npy files from which every counter, bin and 64-bit digest
+    comes back exactly; --steps below 1 (no last step to dump) is refused before anything runs."""
+    import subprocess
+    import sys
+    import bench
+    host = O.synth_reads(0x5EED0002, 0, 3000, 150, 1)
+    st = O.reduce_fused(host, 21, True, True, True)
+    st["sum"], st["xor"] = st["sum"] | (0xFFFF << 48), st["xor"] | 0xFFFF   # digests with all-ones words at both ends
+    bench.dump_outputs(str(tmp_path / "out"), st)
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["counts.npy", "digests.npy", "hist.npy"]
+    arr = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype == np.float64 for a in arr.values())
+    assert arr["hist"].shape == (4096,) and np.array_equal(arr["hist"].astype(np.uint64), np.asarray(st["hist"], dtype=np.uint64))
+    assert [int(v) for v in arr["counts"]] == [st["n_total"], st["n_fwd"], st["n_rc"]]
+    for row, key in zip(arr["digests"], ("sum", "xor")):
+        assert row.shape == (4,) and sum(int(w) << s for w, s in zip(row, (48, 32, 16, 0))) == st[key]
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr, r.stderr[-800:]

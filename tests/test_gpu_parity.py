@@ -1562,7 +1562,7 @@ def test_rccl_all_visible_devices():
         torch.cuda.empty_cache()
 
 
-def test_bench_self_launch_all_devices():
+def test_bench_self_launch_all_devices(tmp_path):
     """`python bench.py --gpus <all visible devices>` end to end as the driver runs it: with more than one device it
     re-launches itself under torch.distributed.run (one process per GPU, the library's own RCCL communicator); with one
     device the same configs[3] path runs as a one-rank RCCL job.  Either way: the whole read set verified against the oracle,
@@ -1574,7 +1574,7 @@ def test_bench_self_launch_all_devices():
     n_dev = torch.cuda.device_count()
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n_dev), "--reads", "8000000", "--steps", "3", "--warmup", "1",
-           "--preheat-ms", "20", "--no-cpu-baseline", "--no-secondary", "--init-timeout-s", "120"]
+           "--preheat-ms", "20", "--no-cpu-baseline", "--no-secondary", "--init-timeout-s", "120", "--dump-outputs", str(tmp_path / "out")]
     if n_dev == 1:   # one rank: the RCCL path needs the rank environment (--gpus 1 alone is the single-GPU configs[1] run)
         env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
         cmd += ["--workload", "c4"]
@@ -1587,6 +1587,10 @@ def test_bench_self_launch_all_devices():
     assert cfg["reads_total"] == 8_000_000 and cfg["seed"] == "0x5eed0004"
     assert line["result"]["verified"] and "bit-exact" in line["result"]["verified"]
     assert line["value"] > 0 and line["roofline"]["frac"] > 0
+    # --dump-outputs: the all-reduced result of the last timed step, the same one the line reports
+    counts, digests = np.load(tmp_path / "out" / "counts.npy"), np.load(tmp_path / "out" / "digests.npy")
+    assert np.load(tmp_path / "out" / "hist.npy").sum() == counts[0] == line["result"]["n_total"] and counts[1] == line["result"]["n_fwd"]
+    assert [hex(sum(int(w) << s for w, s in zip(row, (48, 32, 16, 0)))) for row in digests] == [line["result"]["sum"], line["result"]["xor"]]
 
 
 def test_bench_collective_fallback_is_opt_in():

@@ -206,14 +206,18 @@ void ntk_comm_destroy(ntk_comm *comm);
  * (reference src/lib.rs:22-31, benches/benchmark.rs:32-41,55-64).
  * NTK_PATH_BYTES_CANONICAL with pre = NONE / STRIP_RETURNS (bytes the caller did not normalise): the reference iterator compares RAW
  * bytes (src/kmer.rs:121-128; lower case sorts above upper case), so reduce mode runs a raw-byte kernel for it (slower than the
- * packed-value scan, exact on mixed case); dense values (ntk_materialize_device), quality masking and windowed minimizers on such
- * input are NTK_ERR_UNSUPPORTED - normalize first, as the reference's documented chain does. */
+ * packed-value scan, exact on mixed case); a quality stream (ntk_reduce_device_quality, batches that carry qualities) is masked in
+ * on that route too, at any k; dense values (ntk_materialize_device) and windowed minimizers on such input are NTK_ERR_UNSUPPORTED
+ * (NTK_ERR_BAD_K for k > 32) - normalize first. */
 int ntk_accum_reset(ntk_ctx *ctx);
 int ntk_reduce_device(ntk_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, const ntk_params *p); /* async */
 /* Quality masking fused into the scan: `(seq, qual).quality_mask(cutoff)` (reference
  * src/sequence.rs:285-296: a base whose RAW quality byte is < cutoff becomes N) followed by the chain above, in one pass.
- * d_qual has the layout and alignment of d_seq (one quality byte per sequence byte; the byte under a record's break byte
- * is ignored).  cutoff = bits 15:8 of p->flags; d_qual NULL or cutoff 0 = ntk_reduce_device. */
+ * d_qual has the layout, alignment and readable range of d_seq (one quality byte per sequence byte; the byte under a record's
+ * break byte is ignored).  cutoff = bits 15:8 of p->flags; d_qual NULL or cutoff 0 = ntk_reduce_device.  Every input ntk_reduce_device
+ * takes, with the same k: normalised or not (NTK_PATH_BYTES_CANONICAL with pre = NONE / STRIP_RETURNS: the chain
+ * `(seq, qual).quality_mask(cutoff)` -> canonical_kmers(k, &rc) of src/sequence.rs:237-239, no normalize) and k = 33..255 (counters
+ * + histogram).  A masked lower-case base is an N: it does not send a speculative launch to the byte-walking kernel. */
 int ntk_reduce_device_quality(ntk_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes,
                               const ntk_params *p);                                      /* async */
 int ntk_accum_read(ntk_ctx *ctx, ntk_result *out);            /* synchronises the ctx stream        */

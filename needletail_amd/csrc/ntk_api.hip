@@ -275,25 +275,42 @@ int raw_bytes_blocks(const ntk_ctx *c, uint64_t n)
     return (int)(n_tiles < max_blocks ? n_tiles : max_blocks);
 }
 
-int run_raw_bytes_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, bool zero_first, bool normalized)
+// the quality builds of the byte-walking and k > 32 kernels: (qual, q_add, q_sel) as three trailing arguments (ntk_kernels.hpp QualIn)
+template <bool WIDE> constexpr auto bytes_reduce_q = &canonical_bytes_reduce_kernel<WIDE, true, const uint8_t *, uint32_t, uint32_t>;
+template <bool ACCEPT_U> constexpr auto wide_reduce_q = &wide_canonical_reduce_kernel<ACCEPT_U, true, const uint8_t *, uint32_t, uint32_t>;
+
+// canonical_bytes_reduce_kernel<WIDE> over d_seq[0, n), or its quality build when d_qual is set (masking at `cutoff`, 1..255).
+template <bool WIDE>
+void launch_raw_bytes(ntk_ctx *c, int blocks, const uint8_t *d_seq, uint64_t n, uint32_t k, const uint32_t *run_if, uint32_t normalized,
+                      const uint8_t *d_qual, uint32_t cutoff)
+{
+    const uint32_t pb = k < 6 ? k : 6;
+    if (d_qual) {
+        const QualityCut qc = quality_cut(cutoff);
+        hipLaunchKernelGGL(bytes_reduce_q<WIDE>, dim3(blocks), dim3(kPlThreads), 0, c->stream, d_seq, n, (n + 15) & ~(uint64_t)15, k,
+                           2u * (k - pb), (const uint16_t *)(c->d_lut + 768), c->d_part_hist, c->d_part_scalars, run_if, normalized, d_qual, qc.add, qc.sel);
+    } else {
+        hipLaunchKernelGGL(canonical_bytes_reduce_kernel<WIDE>, dim3(blocks), dim3(kPlThreads), 0, c->stream, d_seq, n, (n + 15) & ~(uint64_t)15, k,
+                           2u * (k - pb), (const uint16_t *)(c->d_lut + 768), c->d_part_hist, c->d_part_scalars, run_if, normalized);
+    }
+}
+
+// d_qual (with cutoff 1..255): the quality stream, masked before the walk (NULL: none).
+int run_raw_bytes_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, bool zero_first, bool normalized,
+                         const uint8_t *d_qual, uint32_t cutoff)
 {
     if (zero_first) HIPCHK(hipMemsetAsync(c->d_acc, 0, NTK_ACC_WORDS * sizeof(uint64_t), c->stream));
     const int blocks = raw_bytes_blocks(c, n);
     int rc = ensure_partials(c, blocks);
     if (rc) return rc;
-    const uint32_t pb = p->k < 6 ? p->k : 6;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing) {
         rc = get_event(c, &e0); if (rc) return rc;
         rc = get_event(c, &e1); if (rc) { c->ev_free.push_back(e0); return rc; }
         HIPCHK(hipEventRecord(e0, c->stream));
     }
-    if (p->k > 32)
-        hipLaunchKernelGGL(canonical_bytes_reduce_kernel<true>, dim3(blocks), dim3(kPlThreads), 0, c->stream, d_seq, n, (n + 15) & ~(uint64_t)15, p->k,
-                           2u * (p->k - pb), (const uint16_t *)(c->d_lut + 768), c->d_part_hist, c->d_part_scalars, (const uint32_t *)nullptr, normalized ? 1u : 0u);
-    else
-        hipLaunchKernelGGL(canonical_bytes_reduce_kernel<false>, dim3(blocks), dim3(kPlThreads), 0, c->stream, d_seq, n, (n + 15) & ~(uint64_t)15, p->k,
-                           2u * (p->k - pb), (const uint16_t *)(c->d_lut + 768), c->d_part_hist, c->d_part_scalars, (const uint32_t *)nullptr, 0u);
+    if (p->k > 32) launch_raw_bytes<true>(c, blocks, d_seq, n, p->k, nullptr, normalized ? 1u : 0u, d_qual, cutoff);
+    else launch_raw_bytes<false>(c, blocks, d_seq, n, p->k, nullptr, 0u, d_qual, cutoff);
     HIPCHK(hipGetLastError());
     if (c->timing) { HIPCHK(hipEventRecord(e1, c->stream)); c->ev_used.emplace_back(e0, e1); }
     hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream,
@@ -307,9 +324,10 @@ int run_raw_bytes_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk
 // 2-bit streams; canonical_bytes_reduce_kernel<true> is queued behind it and returns at once unless that launch raised its flag (two k-mers
 // equal over 32 bases, or - on input that was not normalised - a byte with bit 5 set), and the fold takes whichever partials are valid.  No
 // host round trip; 0.9 ms instead of 9.5 per 1.5 GB at k = 64 (profiles/r06r).  The direct route under NTK_ROUTE_NO_SPECULATION.
-int run_wide_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, bool zero_first, bool normalized)
+int run_wide_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, bool zero_first, bool normalized,
+                    const uint8_t *d_qual, uint32_t cutoff)
 {
-    if (c->route_off & NTK_ROUTE_NO_SPECULATION) return run_raw_bytes_reduce(c, d_seq, n, p, zero_first, normalized);
+    if (c->route_off & NTK_ROUTE_NO_SPECULATION) return run_raw_bytes_reduce(c, d_seq, n, p, zero_first, normalized, d_qual, cutoff);
     if (zero_first) HIPCHK(hipMemsetAsync(c->d_acc, 0, NTK_ACC_WORDS * sizeof(uint64_t), c->stream));
     const uint64_t n_tiles = (n + kWkTile - 1) / kWkTile;
     const uint64_t max_blocks = c->launch_blocks > 0 ? (uint64_t)c->launch_blocks : (uint64_t)c->n_cu * 8;
@@ -325,13 +343,20 @@ int run_wide_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_para
         rc = get_event(c, &e1); if (rc) { c->ev_free.push_back(e0); return rc; }
         HIPCHK(hipEventRecord(e0, c->stream));
     }
-    if (normalized)
+    if (d_qual) {
+        const QualityCut qc = quality_cut(cutoff);
+        if (normalized)
+            hipLaunchKernelGGL(wide_reduce_q<true>, dim3(blocks), dim3(kWkThreads), 0, c->stream, d_seq, n, p->k, c->d_part_hist, c->d_part_scalars,
+                               flag, flag_next, d_qual, qc.add, qc.sel);
+        else
+            hipLaunchKernelGGL(wide_reduce_q<false>, dim3(blocks), dim3(kWkThreads), 0, c->stream, d_seq, n, p->k, c->d_part_hist, c->d_part_scalars,
+                               flag, flag_next, d_qual, qc.add, qc.sel);
+    } else if (normalized)
         hipLaunchKernelGGL(wide_canonical_reduce_kernel<true>, dim3(blocks), dim3(kWkThreads), 0, c->stream, d_seq, n, p->k, c->d_part_hist, c->d_part_scalars, flag, flag_next);
     else
         hipLaunchKernelGGL(wide_canonical_reduce_kernel<false>, dim3(blocks), dim3(kWkThreads), 0, c->stream, d_seq, n, p->k, c->d_part_hist, c->d_part_scalars, flag, flag_next);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(canonical_bytes_reduce_kernel<true>, dim3(blocks_raw), dim3(kPlThreads), 0, c->stream, d_seq, n, (n + 15) & ~(uint64_t)15, p->k,
-                       2u * (p->k - 6u), (const uint16_t *)(c->d_lut + 768), c->d_part_hist, c->d_part_scalars, (const uint32_t *)flag, normalized ? 1u : 0u);
+    launch_raw_bytes<true>(c, blocks_raw, d_seq, n, p->k, (const uint32_t *)flag, normalized ? 1u : 0u, d_qual, cutoff);
     HIPCHK(hipGetLastError());
     if (c->timing) { HIPCHK(hipEventRecord(e1, c->stream)); c->ev_used.emplace_back(e0, e1); }
     hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream,
@@ -358,10 +383,12 @@ int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, 
     const uint64_t kMaxTilesPerLaunch = (uint64_t)8 << 22;
     bool speculate = false;
     if (m.raw_bytes) {
-        // byte path on input that was not normalised: reduce mode only; dense values, quality masking and windowed minimizers on such
-        // input are not built (normalize first, as the reference's documented chain does), and k > 32 has counters + histogram only
-        if (p->k > 32 && (!reduce || cutoff || fused_min_fn)) return NTK_ERR_BAD_K;
-        if (!reduce || cutoff || fused_min_fn) return NTK_ERR_UNSUPPORTED;
+        // byte path on input that was not normalised: reduce mode only; dense values and windowed minimizers on such input are not built
+        // (normalize first, as the reference's documented chain does), and k > 32 has counters + histogram only.  A quality stream is masked
+        // in by every kernel of the route (`(seq, qual).quality_mask(cutoff)` ahead of canonical_kmers, reference src/sequence.rs:237-239,285-296).
+        if (p->k > 32 && (!reduce || fused_min_fn)) return NTK_ERR_BAD_K;
+        if (!reduce || fused_min_fn) return NTK_ERR_UNSUPPORTED;
+        const uint8_t *qual = cutoff ? d_qual : nullptr;
         // k <= 32: the raw-byte order is the 2-bit order unless a base is lower case - the clean read on which Sequence::normalize returns
         // None (reference src/sequence.rs:57-61).  So the packed-value scan runs (its TIE_RC, !ACCEPT_U build watches every byte it loads for
         // bit 5), the raw-byte kernel is queued behind it and returns at once unless the flag went up, and the fold takes whichever partials
@@ -369,8 +396,8 @@ int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, 
         // window starts, the scan on window ends: their launch ranges do not line up), the direct route otherwise and under NTK_ROUTE_NO_SPECULATION.
         const uint64_t tiles_all = ((n + 15) / 16 + tile_slots - 1) / tile_slots;
         speculate = p->k <= 32 && tiles_all <= kMaxTilesPerLaunch && !(c->route_off & NTK_ROUTE_NO_SPECULATION);
-        if (p->k > 32) return run_wide_reduce(c, d_seq, n, p, zero_first, m.accept_u);
-        if (!speculate) return run_raw_bytes_reduce(c, d_seq, n, p, zero_first, false);
+        if (p->k > 32) return run_wide_reduce(c, d_seq, n, p, zero_first, m.accept_u, qual, cutoff);
+        if (!speculate) return run_raw_bytes_reduce(c, d_seq, n, p, zero_first, false, qual, cutoff);
     }
     // materialise mode stages 8.7 KiB per wave through LDS: 256-thread blocks, 4 per CU
     const void *fn = fused_min_fn ? fused_min_fn
@@ -465,9 +492,7 @@ int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, 
         void *kargs[] = {(void *)&a};
         HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(threads), kargs, lds, c->stream));
         if (speculate) {   // (inside the timed span: the pair is this route's scan)
-            const uint32_t pb = p->k < 6 ? p->k : 6;
-            hipLaunchKernelGGL(canonical_bytes_reduce_kernel<false>, dim3(blocks_raw), dim3(kPlThreads), 0, c->stream, d_seq, n, (n + 15) & ~(uint64_t)15, p->k,
-                               2u * (p->k - pb), (const uint16_t *)(c->d_lut + 768), c->d_part_hist, c->d_part_scalars, (const uint32_t *)flag, 0u);
+            launch_raw_bytes<false>(c, blocks_raw, d_seq, n, p->k, (const uint32_t *)flag, 0u, cutoff ? d_qual : nullptr, cutoff);
             HIPCHK(hipGetLastError());
         }
         if (c->timing) {

@@ -749,7 +749,8 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
     // bytes (src/kmer.rs:121-128), which is the 2-bit order as long as no base is lower case - what Sequence::normalize reports by returning
     // None on a clean read (src/sequence.rs:57-61).  The build ORs every byte it loads into `lc` (two full-rate ops per tile); a wave that saw
     // bit 5 anywhere raises a.lower_flag and the host has queued canonical_bytes_reduce_kernel behind this launch, which then redoes it.
-    constexpr bool SPEC = TIE_RC && !ACCEPT_U && !QM && W == 0 && !FWD;
+    // QM: the watch reads the bytes after quality_break and skips masked ones (lower_watch_or: a lower-case base under a low quality is an N).
+    constexpr bool SPEC = TIE_RC && !ACCEPT_U && W == 0 && !FWD;
     uint32_t lc = 0;
     if (SPEC && a.lower_flag_next && blockIdx.x == 0 && threadIdx.x == 0) *a.lower_flag_next = 0;   // the next launch's flag (a ring, see run_scan)
     DevXL xl;
@@ -820,11 +821,15 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
         auto process = [&](const u32x4 &t, const u32x4 &q, uint32_t r, auto &&after_encode) {
             const bool tail = r >= a.tail_tile_rel;
             Raw16 raw{t.x, t.y, t.z, t.w};
-            if constexpr (SPEC) {
+            if constexpr (SPEC && !QM) {
                 if (tail) lc |= or_of_input_bytes(raw, (int64_t)a.n_bytes - ((int64_t)tile_byte - (int64_t)kHaloB + lane * 16));   // (wave-uniform: the last 16-byte line's padding is nobody's base)
                 else lc = bitop3<0xFE>(bitop3<0xFE>(lc, t.x, t.y), t.z, t.w);
             }
             if constexpr (QM) raw = quality_break16(raw, Raw16{q.x, q.y, q.z, q.w}, a.q_add, a.q_sel);
+            if constexpr (SPEC && QM) {
+                if (tail) lc |= or_of_input_bytes(lower_watch16(raw), (int64_t)a.n_bytes - ((int64_t)tile_byte - (int64_t)kHaloB + lane * 16));
+                else lc = lower_watch_or(lower_watch_or(lower_watch_or(lower_watch_or(lc, raw.x), raw.y), raw.z), raw.w);
+            }
 #ifdef NTK_ABL_LOADSONLY
             mp.xlo ^= raw.x ^ raw.y ^ raw.z ^ raw.w; (void)tail;
             after_encode();
@@ -1463,6 +1468,11 @@ __global__ __launch_bounds__(kPlThreads) void canonical_bytes_planes_kernel(cons
     }
 }
 
+// The quality stream of the byte-walking and k > 32 kernels' QM builds: three trailing kernel arguments (qual: the layout, alignment and
+// readable range of seq; add / sel: quality_cut(cutoff)), taken as a parameter pack that is empty in the builds without a quality stream -
+// those keep their argument list and their code.
+struct QualIn { const uint8_t *qual; uint32_t add, sel; };
+
 // CanonicalKmers on bytes the caller did NOT normalise, folded into the accumulators (ntk_reduce_device with NTK_PATH_BYTES_CANONICAL and
 // pre = NONE / STRIP_RETURNS): the reference compares the RAW bytes of the window with the raw bytes of the reverse complement's window
 // (src/kmer.rs:121-128) and lower case sorts above upper case, so on mixed-case input the strand is not the smaller 2-bit value and the
@@ -1477,11 +1487,14 @@ __global__ __launch_bounds__(kPlThreads) void canonical_bytes_planes_kernel(cons
 // counts the k-mers as undigested.  normalized: the batch is to be read as Sequence::normalize would have left it (U / u are T, case
 // folded: src/sequence.rs:24-51), i.e. the strand compare runs on the 2-bit codes; only k > 32 comes here in that form.
 // (WIDE = false: the k <= 32 raw-byte build, whose inner loop carries none of the k > 32 / normalised cases - they cost it 30 %, profiles/r06b.)
-template <bool WIDE>
+// QM: `(seq, qual).quality_mask(cutoff)` first - each staged 16-byte line goes through quality_break16, so a masked byte has bit 7 set, is
+// no base and breaks every window over it; the walk is the same.  The quality stream comes as QualIn's three trailing arguments (QualArgs).
+template <bool WIDE, bool QM = false, class... QualArgs>
 __global__ __launch_bounds__(kPlThreads) void canonical_bytes_reduce_kernel(const uint8_t *seq, uint64_t n, uint64_t n_readable, uint32_t k, uint32_t bin_shift,
                                                                             const uint16_t *comp_lut, uint32_t *part_hist, uint64_t *part_scalars,
-                                                                            const uint32_t *run_if, uint32_t normalized_arg)
+                                                                            const uint32_t *run_if, uint32_t normalized_arg, QualArgs... qual_args)
 {
+    static_assert(sizeof...(QualArgs) == (QM ? 3u : 0u), "QM builds take (qual, q_add, q_sel)");
     if (run_if && *run_if == 0u) return;
     const bool normalized = WIDE && normalized_arg;
     // a thread walks PER starts + k - 1 bytes: 32 starts per thread (the plane kernels' 8 would be 3.5 byte steps per start at k = 21 and 9 at
@@ -1506,7 +1519,15 @@ __global__ __launch_bounds__(kPlThreads) void canonical_bytes_reduce_kernel(cons
         for (uint32_t v = threadIdx.x; v * 16 < need; v += kPlThreads) {
             const uint64_t p = t0 + (uint64_t)v * 16;
             u32x4 x = {0u, 0u, 0u, 0u};
-            if (p + 16 <= n_readable) x = *reinterpret_cast<const u32x4 *>(seq + p);
+            if (p + 16 <= n_readable) {
+                x = *reinterpret_cast<const u32x4 *>(seq + p);
+                if constexpr (QM) {
+                    const QualIn qi{qual_args...};
+                    const u32x4 q = *reinterpret_cast<const u32x4 *>(qi.qual + p);
+                    const Raw16 m = quality_break16(Raw16{x.x, x.y, x.z, x.w}, Raw16{q.x, q.y, q.z, q.w}, qi.add, qi.sel);
+                    x = u32x4{m.x, m.y, m.z, m.w};
+                }
+            }
             *reinterpret_cast<u32x4 *>(&s_b[v * 16]) = x;
         }
         __syncthreads();
@@ -1601,10 +1622,15 @@ __device__ __forceinline__ int32_t wk_wave_scan_max(int32_t x)
     x = wk_dpp_max<0x142, 0xA>(x);
     return wk_dpp_max<0x143, 0xC>(x);
 }
-template <bool ACCEPT_U>
+// QM: `(seq, qual).quality_mask(cutoff)` first - each slot goes through quality_break16 before it is encoded (a masked byte is a break),
+// and the bit-5 watch skips masked bytes (lower_watch16).  The tie watch needs nothing: a masked base breaks every window over it.  The
+// quality stream comes as QualIn's three trailing arguments (QualArgs).
+template <bool ACCEPT_U, bool QM = false, class... QualArgs>
 __global__ __launch_bounds__(kWkThreads) void wide_canonical_reduce_kernel(const uint8_t *seq, uint64_t n, uint32_t k, uint32_t *part_hist,
-                                                                           uint64_t *part_scalars, uint32_t *redo_flag, uint32_t *redo_flag_next)
+                                                                           uint64_t *part_scalars, uint32_t *redo_flag, uint32_t *redo_flag_next,
+                                                                           QualArgs... qual_args)
 {
+    static_assert(sizeof...(QualArgs) == (QM ? 3u : 0u), "QM builds take (qual, q_add, q_sel)");
     __shared__ uint32_t s_code[kWkSlots + 2], s_rcode[kWkSlots];
     __shared__ uint32_t s_hist[kHistBins];
     __shared__ int32_t s_wmax[kWkThreads / 64 + 1];
@@ -1624,8 +1650,17 @@ __global__ __launch_bounds__(kWkThreads) void wide_canonical_reduce_kernel(const
         auto stage = [&](int32_t s, uint32_t &bad) -> int32_t {   // encodes slot s; returns the staged position of its last break (-1: none)
             const int64_t p = t0 + 16 * (int64_t)s;
             u32x4 x = {0u, 0u, 0u, 0u};
-            if (p >= 0 && (uint64_t)p + 16 <= n_readable) x = *reinterpret_cast<const u32x4 *>(seq + p);
-            const WkSlot sl = wk_stage_slot<ACCEPT_U>(Raw16{x.x, x.y, x.z, x.w}, s, p < 0 ? 0 : (int64_t)n - p);   // bytes before the input or at / beyond n are breaks
+            Raw16 raw;
+            if constexpr (QM) {
+                const QualIn qi{qual_args...};
+                u32x4 q = {0u, 0u, 0u, 0u};
+                if (p >= 0 && (uint64_t)p + 16 <= n_readable) { x = *reinterpret_cast<const u32x4 *>(seq + p); q = *reinterpret_cast<const u32x4 *>(qi.qual + p); }
+                raw = quality_break16(Raw16{x.x, x.y, x.z, x.w}, Raw16{q.x, q.y, q.z, q.w}, qi.add, qi.sel);
+            } else {
+                if (p >= 0 && (uint64_t)p + 16 <= n_readable) x = *reinterpret_cast<const u32x4 *>(seq + p);
+                raw = Raw16{x.x, x.y, x.z, x.w};
+            }
+            const WkSlot sl = wk_stage_slot<ACCEPT_U, QM>(raw, s, p < 0 ? 0 : (int64_t)n - p);   // bytes before the input or at / beyond n are breaks
             if (!ACCEPT_U) lc |= sl.or_bytes;
             bad = sl.bad;
             s_code[s] = sl.code; s_rcode[s] = sl.rcode;

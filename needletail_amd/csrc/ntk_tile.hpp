@@ -206,6 +206,15 @@ NTK_HD Raw16 quality_break16(Raw16 s, Raw16 q, uint32_t add, uint32_t sel)
     return Raw16{quality_break(s.x, q.x, add, sel), quality_break(s.y, q.y, add, sel),
                  quality_break(s.z, q.z, add, sel), quality_break(s.w, q.w, add, sel)};
 }
+// The speculative kernels' bit-5 watch ("a lower-case byte was seen") on bytes that went through quality_break: a byte counts when bit 5
+// is set and bit 7 is not.  quality_break sets bit 7 of a masked byte and leaves bit 5 alone, so a lower-case base under a low quality
+// (an N to every later step) does not send a launch to the byte-walking kernel; a byte that had bit 7 to begin with is no base either.
+// Bit 5 of each byte of the result is the watched bit (bit 7 of the same byte lands on bit 5 of `m >> 2`).
+NTK_HD uint32_t lower_watch_or(uint32_t lc, uint32_t m) { return bitop3<0xF4>(lc, m, m >> 2); }   // lc | (m & ~(m >> 2)): 2 full-rate ops
+NTK_HD Raw16 lower_watch16(Raw16 m)
+{
+    return Raw16{lower_watch_or(0u, m.x), lower_watch_or(0u, m.y), lower_watch_or(0u, m.z), lower_watch_or(0u, m.w)};
+}
 struct Enc {
     uint32_t code;   // 2-bit codes, MSB-first
     uint32_t rcode;  // group g (bits 2g+1:2g) = complement of base g: the reverse-complement stream word
@@ -1284,14 +1293,16 @@ NTK_HD uint32_t or_of_input_bytes(Raw16 raw, int64_t keep)
 
 // One slot: `keep` = how many of its 16 bytes belong to the input (<= 0: none - before the input's start or beyond its end; >= 16: all).
 // Returns the staged position of the slot's last break, -1 if it holds none.
+// QM: raw went through quality_break16 - or_bytes then ORs the watch bytes of lower_watch16 (masked bytes do not count).
 struct WkSlot { uint32_t code, rcode, bad, or_bytes; int32_t last_break; };   // bad: base i at bit 15 - i; or_bytes: OR of the slot's input bytes
-template <bool ACCEPT_U>
+template <bool ACCEPT_U, bool QM = false>
 NTK_HD WkSlot wk_stage_slot(Raw16 raw, int32_t slot, int64_t keep)
 {
     const EncSV2 en = encode16_sv2<ACCEPT_U>(raw);
     WkSlot r;
     r.code = en.code; r.rcode = en.rcode;
-    r.or_bytes = or_of_input_bytes(raw, keep);
+    if constexpr (QM) r.or_bytes = or_of_input_bytes(lower_watch16(raw), keep);
+    else r.or_bytes = or_of_input_bytes(raw, keep);
     r.bad = bad16_from_letters(en.ex, en.uu);
     if (keep <= 0) r.bad = 0xFFFFu;
     else if (keep < 16) r.bad |= 0xFFFFu >> (uint32_t)keep;

@@ -82,7 +82,9 @@ class Context:
     def reduce_device(self, d_seq, n_bytes: int, k: int, path: int, pre: int, w: int = 0, d_qual=None,
                       quality_cutoff: int = 0, reset: bool = False):
         """w > 0: fold windowed minimizers (w k-mers per window) instead of every k-mer.  d_qual + quality_cutoff: mask
-        bases whose quality byte is below the cutoff first (QualitySequence::quality_mask, reference src/sequence.rs:285-296).
+        bases whose quality byte is below the cutoff first (QualitySequence::quality_mask, reference src/sequence.rs:285-296) - on
+        every input this call takes: normalised or not (PATH_BYTES_CANONICAL with PRE_NONE / PRE_STRIP_RETURNS is the FASTQ chain
+        quality_mask -> canonical_kmers), and k = 33..255.
         reset: start a new result (NTK_FLAG_RESET: accum_reset() folded into this call's kernel launch)."""
         p = L.Params(k, path, pre, L.flags(w, quality_cutoff, reset))
         if d_qual is None:

@@ -230,20 +230,21 @@ const void *pick_scan(const Mode &m, uint32_t k)
         if (QM) return ntk_pick_scan2_q((int)k, m.canon, m.tie_rc, m.accept_u);
         return m.canon ? ntk_pick_scan2((int)k, m.tie_rc, m.accept_u) : ntk_pick_scan2_fwd((int)k, m.accept_u);
     } else {
+        // (no TIE_RC && !ACCEPT_U build: that is the byte path on input that was not normalised, which materialise mode rejects - run_scan)
 #define NTK_PICK_FIX(KF, T, U)                                                                      \
     if (!QM && m.kw == 2 && m.canon && k == KF && m.tie_rc == T && m.accept_u == U)                  \
         return (const void *)&scan_kernel<2, true, T, U, false, KF>;
-    NTK_PICK_FIX(21, false, false) NTK_PICK_FIX(21, false, true) NTK_PICK_FIX(21, true, false) NTK_PICK_FIX(21, true, true)
+    NTK_PICK_FIX(21, false, false) NTK_PICK_FIX(21, false, true) NTK_PICK_FIX(21, true, true)
 #undef NTK_PICK_FIX
 #define NTK_PICK(KW, C, T, U)                                                                       \
     if (m.kw == KW && m.canon == C && m.tie_rc == T && m.accept_u == U)                             \
         return (const void *)&scan_kernel<KW, C, T, U, false, 0, QM>;
     NTK_PICK(1, false, false, false) NTK_PICK(1, false, false, true)
     NTK_PICK(1, true, false, false) NTK_PICK(1, true, false, true)
-    NTK_PICK(1, true, true, false) NTK_PICK(1, true, true, true)
+    NTK_PICK(1, true, true, true)
     NTK_PICK(2, false, false, false) NTK_PICK(2, false, false, true)
     NTK_PICK(2, true, false, false) NTK_PICK(2, true, false, true)
-    NTK_PICK(2, true, true, false) NTK_PICK(2, true, true, true)
+    NTK_PICK(2, true, true, true)
 #undef NTK_PICK
     return nullptr;
     }
@@ -517,13 +518,14 @@ const void *pick_min_generic(const Mode &m, bool quality, bool f64, uint32_t k) 
     const int kw = f64 ? 2 : m.kw;   // (the f64 keys are built from the code streams for any k: one instantiation serves both word counts)
     const int mode = min_gen_mode(k, f64);
 #define NTK_PICK_MG(KW, T, U, Q, F, MD) if (kw == KW && m.tie_rc == T && m.accept_u == U && quality == Q && f64 == F && mode == MD) return (const void *)&minimizer_scan_kernel<KW, T, U, Q, F, MD>;
-#define NTK_PICK_MG4(KW, Q, F, MD) NTK_PICK_MG(KW, false, false, Q, F, MD) NTK_PICK_MG(KW, false, true, Q, F, MD) NTK_PICK_MG(KW, true, false, Q, F, MD) NTK_PICK_MG(KW, true, true, Q, F, MD)
-#define NTK_PICK_MG8(KW, F, MD) NTK_PICK_MG4(KW, false, F, MD) NTK_PICK_MG4(KW, true, F, MD)
-    NTK_PICK_MG8(2, true, 0) NTK_PICK_MG8(2, true, 1) NTK_PICK_MG8(2, true, 3) NTK_PICK_MG8(2, true, 2)   // f64 keys: k <= 7, 8..18, 19..23, 24..25
-    NTK_PICK_MG8(2, false, 2)                                                                             // 26 <= k <= 31
-    NTK_PICK_MG8(2, false, 1) NTK_PICK_MG8(1, false, 0) NTK_PICK_MG8(1, false, 1)                         // (only under NTK_ROUTE_NO_F64, the A/B switch)
-#undef NTK_PICK_MG8
-#undef NTK_PICK_MG4
+// (no TIE_RC && !ACCEPT_U build: the byte path on input that was not normalised never gets here - minimizers_reduce_impl rejects it)
+#define NTK_PICK_MG3(KW, Q, F, MD) NTK_PICK_MG(KW, false, false, Q, F, MD) NTK_PICK_MG(KW, false, true, Q, F, MD) NTK_PICK_MG(KW, true, true, Q, F, MD)
+#define NTK_PICK_MG6(KW, F, MD) NTK_PICK_MG3(KW, false, F, MD) NTK_PICK_MG3(KW, true, F, MD)
+    NTK_PICK_MG6(2, true, 0) NTK_PICK_MG6(2, true, 1) NTK_PICK_MG6(2, true, 3) NTK_PICK_MG6(2, true, 2)   // f64 keys: k <= 7, 8..18, 19..23, 24..25
+    NTK_PICK_MG6(2, false, 2)                                                                             // 26 <= k <= 31
+    NTK_PICK_MG6(2, false, 1) NTK_PICK_MG6(1, false, 0) NTK_PICK_MG6(1, false, 1)                         // (only under NTK_ROUTE_NO_F64, the A/B switch)
+#undef NTK_PICK_MG6
+#undef NTK_PICK_MG3
 #undef NTK_PICK_MG
     return nullptr;
 }

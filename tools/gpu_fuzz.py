@@ -27,7 +27,10 @@ MODES = [  # (path, pre, canonical, tie_rc, accept_u)
     (nt.PATH_BITS, nt.PRE_STRIP_RETURNS, False, False, False),
     (nt.PATH_BITS_CANONICAL, nt.PRE_NORMALIZE_IUPAC, True, False, True),
     (nt.PATH_BYTES_CANONICAL, nt.PRE_NORMALIZE_IUPAC, True, True, True),
+    (nt.PATH_BITS, nt.PRE_NORMALIZE, False, False, True),
+    (nt.PATH_BITS_CANONICAL, nt.PRE_NORMALIZE, True, False, True),
 ]
+MIN_MODES = [MODES[0], MODES[1], MODES[6]]   # windowed minimizers: canonical paths; (BITS_CANONICAL, NORMALIZE) has ties -> fwd with U accepted
 EDGE = [0, 1, 2, 15, 16, 17, 31, 32, 33, 150, 151, 991, 992, 993, 1007, 1008, 1009, 1023, 1024, 1025, 1984, 2016, 2048,
         992 * 24 - 1, 992 * 24, 992 * 24 + 1]
 JUNK = np.frombuffer(b"NnUuRYKMSWBDHVrykm-.*\x00\x7f\x80\xff0@>+", dtype=np.uint8)
@@ -122,7 +125,7 @@ def main():
         what = rng.integers(0, 10)
         if args.minimizers_only:
             what = 6
-            path, pre, canon, tie, u = MODES[int(rng.integers(0, 2))]
+            path, pre, canon, tie, u = MIN_MODES[int(rng.integers(0, len(MIN_MODES)))]
         # launch geometry: mostly the library's choice, sometimes forced (few / many blocks, small / large blocks: the shard, chunk
         # and work-counter arithmetic of the scan must not depend on it)
         launch = (int(rng.choice([1, 2, 7, 64, 300, 512, 1024, 2048])), int(rng.choice([0, 64, 128, 256, 512, 768, 1024]))) if rng.random() < 0.3 else (0, 0)
@@ -140,7 +143,7 @@ def main():
                 if path == nt.PATH_BYTES_CANONICAL and rng.random() < 0.3: rng.choice([0, 0, 0, 33, 48, 64, 255]); rng.integers(0, 2)
             elif what < 6 and n <= 400000:
                 pass
-            elif what < 8 and canon and (path, pre) in ((nt.PATH_BYTES_CANONICAL, nt.PRE_NORMALIZE), (nt.PATH_BITS_CANONICAL, nt.PRE_NONE)):
+            elif what < 8 and canon and (path, pre) in [m[:2] for m in MIN_MODES]:
                 if rng.random() < 0.4:
                     if rng.random() < 0.5: rng.choice([1, 2, 5, 9, 10, 11, 12, 16, 33])
                     if not rng.random() < 0.5: rng.choice([15, 16, 17, 18, 19, 20, 21, 22, 23])
@@ -226,7 +229,7 @@ def main():
                     and got_xor == int(want["xor"])):
                 print("MISMATCH materialize", tag); return 1
             counts["materialize"] += 1
-        elif what < 8 and canon and (path, pre) in ((nt.PATH_BYTES_CANONICAL, nt.PRE_NORMALIZE), (nt.PATH_BITS_CANONICAL, nt.PRE_NONE)):
+        elif what < 8 and canon and (path, pre) in [m[:2] for m in MIN_MODES]:
             u4 = rng.random()
             if u4 < 0.4:     # the register-fused grid and its edges
                 w = int(rng.choice([1, 2, 5, 9, 10, 11, 12, 16, 33])) if rng.random() < 0.5 else 11

@@ -130,6 +130,9 @@ int ntk_ctx_create(int device, ntk_ctx **out);
 int ntk_ctx_create_on_stream(int device, void *hip_stream, ntk_ctx **out);
 void ntk_ctx_destroy(ntk_ctx *ctx);
 int ntk_ctx_synchronize(ntk_ctx *ctx);
+/* The ctx's device and HIP stream (a hipStream_t; NULL = the default stream): for libraries that enqueue their own kernels in order
+ * with the ctx's work (libneedletail_amd_count.so). */
+int ntk_ctx_stream(ntk_ctx *ctx, int *device, void **hip_stream);
 /* Launch geometry of the scan kernel: blocks (0 = auto: the resident grid) x threads per block (a multiple of 64 up to
  * 1024; 0 = auto: the largest of 768 / 640 / 512 that keeps two blocks of a reduce build resident per CU - 768 for every shipped
  * build; materialise mode always runs 256-thread blocks). */

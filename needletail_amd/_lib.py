@@ -28,7 +28,7 @@ ROUTE_TWO_PASS = ROUTE_NO_REGFUSED | ROUTE_NO_GENERIC
 SYMBOLS = [
     "ntk_strerror", "ntk_last_hip_error", "ntk_last_rccl_error", "ntk_abi_version", "ntk_device_count",
     "ntk_comm_init_all", "ntk_comm_unique_id", "ntk_comm_init_rank", "ntk_comm_size", "ntk_allreduce_accumulators", "ntk_comm_allreduce_time_ms", "ntk_comm_destroy",
-    "ntk_ctx_create", "ntk_ctx_create_on_stream", "ntk_ctx_destroy", "ntk_ctx_synchronize",
+    "ntk_ctx_create", "ntk_ctx_create_on_stream", "ntk_ctx_destroy", "ntk_ctx_synchronize", "ntk_ctx_stream",
     "ntk_ctx_set_launch", "ntk_ctx_set_option", "ntk_ctx_get_option", "ntk_ctx_enable_timing", "ntk_ctx_scan_time_ms",
     "ntk_accum_reset", "ntk_reduce_device", "ntk_reduce_device_quality", "ntk_accum_read", "ntk_accum_device_ptr", "ntk_accum_bind_device",
     "ntk_materialize_device", "ntk_materialize_device_quality",
@@ -118,6 +118,7 @@ def lib() -> C.CDLL:
     L.ntk_ctx_destroy.restype = None
     L.ntk_ctx_destroy.argtypes = [vp]
     L.ntk_ctx_synchronize.argtypes = [vp]
+    L.ntk_ctx_stream.argtypes = [vp, C.POINTER(i32), pp]
     L.ntk_ctx_set_launch.argtypes = [vp, i32, i32]
     L.ntk_ctx_set_option.argtypes = [vp, i32, u64]
     L.ntk_ctx_enable_timing.argtypes = [vp, i32]

@@ -742,6 +742,14 @@ int ntk_ctx_synchronize(ntk_ctx *c)
     return NTK_OK;
 }
 
+int ntk_ctx_stream(ntk_ctx *c, int *device, void **hip_stream)
+{
+    if (!c || !device || !hip_stream) return NTK_ERR_BAD_ARG;
+    *device = c->device;
+    *hip_stream = (void *)c->stream;
+    return NTK_OK;
+}
+
 int ntk_ctx_set_launch(ntk_ctx *c, int blocks, int threads)
 {
     if (!c || blocks < 0 || threads < 0 || threads > 1024 || (threads & 63)) return NTK_ERR_BAD_ARG;   // threads 0 = automatic

@@ -1,0 +1,486 @@
+// Exact k-mer count table on the device (include/needletail_amd_count.h).  A consumer of the core's public ABI: the keys are the values
+// ntk_materialize_device_quality emits, so every path's canonical form and tie rule are the core's by construction.
+//
+// Table: structure of arrays, keys[slots] (EMPTY = ~0) and counts[slots], 16 B per slot; slot = fmix64(key) & (slots - 1), then
+// linear probing, at most kProbeMax slots.  Keys are write-once (EMPTY -> key, claimed by an agent-scope CAS), counts change only
+// through agent-scope atomics.  The one key that equals EMPTY (NTK_PATH_BITS, k = 32, TTT...T) is counted in a side word.
+// DESIGN.md section 10 has the layout, the coherence argument and the chunking.
+#include "../../include/needletail_amd_count.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <new>
+#include <rocprim/device/device_radix_sort.hpp>
+
+namespace {
+
+constexpr uint64_t kEmpty = ~(uint64_t)0;
+constexpr uint32_t kProbeMax = 4096;                     // probe bound: a full or adversarial table never makes a kernel run long
+constexpr uint64_t kChunkBases = (uint64_t)64 << 20;     // bases materialised per pass (scratch: 10 B per base)
+constexpr int kThreads = 256;
+constexpr uint32_t kExtractPerThread = 32;               // slots per thread of the extract count / scatter kernels
+constexpr uint64_t kExtractPerBlock = (uint64_t)kThreads * kExtractPerThread;
+constexpr uint32_t kMaxBins = 16384;
+// stats words on the device
+constexpr int kStDistinct = 0, kStTotal = 1, kStDropped = 2, kStOnes = 3, kStWords = 4;
+
+#define KT_HIPCHK(expr)                      \
+    do {                                     \
+        hipError_t e__ = (expr);             \
+        if (e__ != hipSuccess) {             \
+            (void)hipGetLastError();         \
+            return NTK_ERR_HIP;              \
+        }                                    \
+    } while (0)
+
+__host__ __device__ inline uint64_t fmix64(uint64_t x)
+{
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+__device__ inline uint64_t wave_sum(uint64_t v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ inline void add_agent(uint64_t *p, uint64_t v)
+{
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+struct InsertArgs {
+    const uint64_t *values;    // materialised values, indexed by window end
+    const uint16_t *valid16;   // bit (15 - e % 16) of word e / 16: window e is emitted
+    uint64_t first, n;         // windows ending in [first, n) are inserted (first: the chunk's halo)
+    uint64_t *keys, *counts, *stats;
+    uint64_t mask;
+    uint32_t probe_max;
+};
+
+// One window end per lane, grid-stride; every lane of a wave runs the same number of iterations (the bound is rounded up to the
+// grid), so the counters are summed across the wave once at the end and added by one lane.
+__global__ __launch_bounds__(kThreads) void kt_insert_kernel(InsertArgs a)
+{
+    uint64_t distinct = 0, total = 0, dropped = 0, ones = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, span = a.n - a.first;
+    const uint64_t rounds = (span + stride - 1) / stride;
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t r = 0; r < rounds; r++, i += stride) {
+        if (i >= span) continue;
+        const uint64_t e = a.first + i;
+        if (!((a.valid16[e >> 4] >> (15 - (e & 15))) & 1u)) continue;
+        const uint64_t key = a.values[e];
+        if (key == kEmpty) { ones++; total++; continue; }
+        uint64_t slot = fmix64(key) & a.mask;
+        uint32_t p = 0;
+        for (; p < a.probe_max; p++, slot = (slot + 1) & a.mask) {
+            // a plain load sees EMPTY or the slot's final key (write-once); EMPTY may be stale in this XCD's L2, so only the CAS's
+            // returned value decides whether the slot is ours, already this key, or another key's
+            uint64_t cur = a.keys[slot];
+            if (cur == kEmpty) {
+                uint64_t expected = kEmpty;
+                if (__hip_atomic_compare_exchange_strong(&a.keys[slot], &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                         __HIP_MEMORY_SCOPE_AGENT)) {
+                    distinct++;
+                    cur = key;
+                } else {
+                    cur = expected;
+                }
+            }
+            if (cur == key) {
+                add_agent(&a.counts[slot], 1);
+                total++;
+                break;
+            }
+        }
+        if (p == a.probe_max) dropped++;
+    }
+    distinct = wave_sum(distinct); total = wave_sum(total); dropped = wave_sum(dropped); ones = wave_sum(ones);
+    if ((threadIdx.x & 63) == 0) {
+        if (distinct) add_agent(a.stats + kStDistinct, distinct);
+        if (total) add_agent(a.stats + kStTotal, total);
+        if (dropped) add_agent(a.stats + kStDropped, dropped);
+        if (ones) add_agent(a.stats + kStOnes, ones);
+    }
+}
+
+__device__ inline uint32_t block_sum_u32(uint32_t v, uint32_t *lds)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t s = 0;
+    for (int w = 0; w < kThreads / 64; w++) s += lds[w];
+    return s;
+}
+
+// extract, step 1: occupied slots with count >= min_count, per block of kExtractPerBlock slots
+__global__ __launch_bounds__(kThreads) void kt_extract_count_kernel(const uint64_t *keys, const uint64_t *counts, uint64_t slots,
+                                                                    uint64_t min_count, uint32_t *block_counts)
+{
+    __shared__ uint32_t lds[kThreads / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * kExtractPerBlock;
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < kExtractPerThread; j++) {
+        const uint64_t s = base + (uint64_t)j * kThreads + threadIdx.x;
+        if (s < slots && keys[s] != kEmpty && counts[s] >= min_count) c++;
+    }
+    c = block_sum_u32(c, lds);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = c;
+}
+
+// extract, step 2: exclusive scan of the block counts (one block); offsets[nb] = the total
+__global__ __launch_bounds__(1024) void kt_extract_scan_kernel(const uint32_t *block_counts, uint32_t nb, uint64_t *offsets)
+{
+    __shared__ uint64_t part[1024];
+    const uint32_t per = (nb + 1023) / 1024, lo = threadIdx.x * per, hi = lo + per < nb ? lo + per : nb;
+    uint64_t s = 0;
+    for (uint32_t b = lo; b < hi; b++) s += block_counts[b];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan of the 1024 partial sums
+        const uint64_t v = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint64_t run = part[threadIdx.x] - s;
+    for (uint32_t b = lo; b < hi; b++) { offsets[b] = run; run += block_counts[b]; }
+    if (threadIdx.x == 1023) offsets[nb] = part[1023];
+}
+
+// extract, step 3: scatter the pairs of each block to its offset (order inside a block is arbitrary: the sort follows)
+__global__ __launch_bounds__(kThreads) void kt_extract_scatter_kernel(const uint64_t *keys, const uint64_t *counts, uint64_t slots,
+                                                                      uint64_t min_count, const uint64_t *offsets, uint64_t *out_keys,
+                                                                      uint64_t *out_counts)
+{
+    __shared__ uint32_t fill;
+    if (threadIdx.x == 0) fill = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kExtractPerBlock, at = offsets[blockIdx.x];
+    for (uint32_t j = 0; j < kExtractPerThread; j++) {
+        const uint64_t s = base + (uint64_t)j * kThreads + threadIdx.x;
+        if (s >= slots) continue;
+        const uint64_t key = keys[s], c = counts[s];
+        if (key != kEmpty && c >= min_count) {
+            const uint32_t pos = atomicAdd(&fill, 1u);
+            out_keys[at + pos] = key;
+            out_counts[at + pos] = c;
+        }
+    }
+}
+
+// spectrum: a block-private LDS histogram over a grid-stride share of the slots, then one atomic per non-zero bin per block
+__global__ __launch_bounds__(kThreads) void kt_spectrum_kernel(const uint64_t *keys, const uint64_t *counts, uint64_t slots,
+                                                               uint32_t n_bins, uint64_t *hist)
+{
+    extern __shared__ uint32_t bins[];
+    for (uint32_t b = threadIdx.x; b < n_bins; b += blockDim.x) bins[b] = 0;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += stride) {
+        if (keys[s] == kEmpty) continue;
+        const uint64_t c = counts[s];
+        atomicAdd(&bins[c < n_bins - 1 ? (uint32_t)c : n_bins - 1], 1u);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < n_bins; b += blockDim.x)
+        if (bins[b]) add_agent(hist + b, bins[b]);
+}
+
+// lookup: read-only probe; the EMPTY key reads the side word
+__global__ __launch_bounds__(kThreads) void kt_lookup_kernel(const uint64_t *keys, const uint64_t *counts, uint64_t mask,
+                                                             uint32_t probe_max, uint64_t ones, const uint64_t *queries, uint64_t n,
+                                                             uint64_t *out)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t q = queries[i];
+        uint64_t c = 0;
+        if (q == kEmpty) {
+            c = ones;
+        } else {
+            uint64_t slot = fmix64(q) & mask;
+            for (uint32_t p = 0; p < probe_max; p++, slot = (slot + 1) & mask) {
+                const uint64_t cur = keys[slot];
+                if (cur == q) { c = counts[slot]; break; }
+                if (cur == kEmpty) break;
+            }
+        }
+        out[i] = c;
+    }
+}
+
+inline unsigned grid_for(uint64_t items, unsigned block, unsigned cap)
+{
+    const uint64_t b = (items + block - 1) / block;
+    return (unsigned)(b > cap ? cap : (b ? b : 1));
+}
+
+int alloc_status(hipError_t e)
+{
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? NTK_ERR_NOMEM : NTK_ERR_HIP;
+}
+
+}  // namespace
+
+struct ntk_kmer_table {
+    ntk_ctx *ctx = nullptr;
+    int device = 0, n_cu = 256;
+    hipStream_t stream = nullptr;
+    uint32_t k = 0, path = 0, probe_max = kProbeMax;
+    uint64_t slots = 0;
+    uint64_t *d_keys = nullptr, *d_counts = nullptr;
+    uint64_t *d_stats = nullptr, *d_hist = nullptr, *d_offsets = nullptr;
+    uint32_t *d_block_counts = nullptr;
+    uint64_t *h_stage = nullptr;   // pinned: stats and spectrum read-backs
+    // materialise scratch of one chunk (grown on demand)
+    uint64_t scratch_bytes = 0;
+    uint64_t *d_values = nullptr;
+    uint16_t *d_valid16 = nullptr, *d_rc16 = nullptr;
+};
+
+namespace {
+
+void free_scratch(ntk_kmer_table *t)
+{
+    if (t->d_values) (void)hipFree(t->d_values);
+    if (t->d_valid16) (void)hipFree(t->d_valid16);
+    if (t->d_rc16) (void)hipFree(t->d_rc16);
+    t->d_values = nullptr; t->d_valid16 = t->d_rc16 = nullptr; t->scratch_bytes = 0;
+}
+
+int ensure_scratch(ntk_kmer_table *t, uint64_t len)
+{
+    const uint64_t need = (len + 15) & ~(uint64_t)15;
+    if (need <= t->scratch_bytes) return NTK_OK;
+    KT_HIPCHK(hipStreamSynchronize(t->stream));   // the old scratch may still be read by queued kernels
+    free_scratch(t);
+    hipError_t e;
+    if ((e = hipMalloc((void **)&t->d_values, need * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc((void **)&t->d_valid16, need / 16 * sizeof(uint16_t))) != hipSuccess ||
+        (e = hipMalloc((void **)&t->d_rc16, need / 16 * sizeof(uint16_t))) != hipSuccess) {
+        free_scratch(t);
+        return alloc_status(e);
+    }
+    t->scratch_bytes = need;
+    return NTK_OK;
+}
+
+uint64_t extract_blocks(const ntk_kmer_table *t) { return (t->slots + kExtractPerBlock - 1) / kExtractPerBlock; }
+
+// stats words on the host (synchronises)
+int read_stats(ntk_kmer_table *t, uint64_t *w)
+{
+    KT_HIPCHK(hipSetDevice(t->device));
+    KT_HIPCHK(hipMemcpyAsync(t->h_stage, t->d_stats, kStWords * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+    KT_HIPCHK(hipStreamSynchronize(t->stream));
+    memcpy(w, t->h_stage, kStWords * sizeof(uint64_t));
+    return NTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ntk_kmer_table_create(ntk_ctx *ctx, uint32_t k, uint32_t path, uint64_t capacity, ntk_kmer_table **out)
+{
+    if (!ctx || !out) return NTK_ERR_BAD_ARG;
+    *out = nullptr;
+    if (k < 1 || k > 32) return NTK_ERR_BAD_K;
+    if (path > NTK_PATH_BITS_CANONICAL || capacity == 0 || capacity > ((uint64_t)3 << 38)) return NTK_ERR_BAD_ARG;
+    ntk_kmer_table *t = new (std::nothrow) ntk_kmer_table();
+    if (!t) return NTK_ERR_NOMEM;
+    void *stream = nullptr;
+    int rc = ntk_ctx_stream(ctx, &t->device, &stream);
+    if (rc) { delete t; return rc; }
+    t->ctx = ctx; t->stream = (hipStream_t)stream; t->k = k; t->path = path;
+    t->slots = 2;
+    while (capacity * 4 > t->slots * 3) t->slots <<= 1;   // capacity <= 0.75 * slots
+    t->probe_max = t->slots < kProbeMax ? (uint32_t)t->slots : kProbeMax;
+    hipError_t e = hipSetDevice(t->device);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&t->n_cu, hipDeviceAttributeMultiprocessorCount, t->device);
+    if (e != hipSuccess) { (void)hipGetLastError(); delete t; return NTK_ERR_HIP; }
+    const uint64_t nb = extract_blocks(t);
+    if ((e = hipMalloc((void **)&t->d_keys, t->slots * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc((void **)&t->d_counts, t->slots * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc((void **)&t->d_stats, kStWords * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc((void **)&t->d_hist, kMaxBins * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc((void **)&t->d_offsets, (nb + 1) * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc((void **)&t->d_block_counts, nb * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipHostMalloc((void **)&t->h_stage, kMaxBins * sizeof(uint64_t), hipHostMallocDefault)) != hipSuccess) {
+        rc = alloc_status(e);
+        ntk_kmer_table_destroy(t);
+        return rc;
+    }
+    rc = ntk_kmer_table_reset(t);
+    if (rc) { ntk_kmer_table_destroy(t); return rc; }
+    *out = t;
+    return NTK_OK;
+}
+
+void ntk_kmer_table_destroy(ntk_kmer_table *t)
+{
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    (void)hipStreamSynchronize(t->stream);
+    free_scratch(t);
+    for (void *p : {(void *)t->d_keys, (void *)t->d_counts, (void *)t->d_stats, (void *)t->d_hist, (void *)t->d_offsets,
+                    (void *)t->d_block_counts})
+        if (p) (void)hipFree(p);
+    if (t->h_stage) (void)hipHostFree(t->h_stage);
+    (void)hipGetLastError();
+    delete t;
+}
+
+int ntk_kmer_table_reset(ntk_kmer_table *t)
+{
+    if (!t) return NTK_ERR_BAD_ARG;
+    KT_HIPCHK(hipSetDevice(t->device));
+    KT_HIPCHK(hipMemsetAsync(t->d_keys, 0xFF, t->slots * sizeof(uint64_t), t->stream));
+    KT_HIPCHK(hipMemsetAsync(t->d_counts, 0, t->slots * sizeof(uint64_t), t->stream));
+    KT_HIPCHK(hipMemsetAsync(t->d_stats, 0, kStWords * sizeof(uint64_t), t->stream));
+    return NTK_OK;
+}
+
+int ntk_kmer_table_count_device(ntk_kmer_table *t, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes, const ntk_params *p)
+{
+    if (!t || !p) return NTK_ERR_BAD_ARG;
+    if (p->k != t->k || p->path != t->path || (p->flags & ~0xFF00u) != 0 || p->pre > NTK_PRE_NORMALIZE_IUPAC) return NTK_ERR_BAD_ARG;
+    if (p->path == NTK_PATH_BYTES_CANONICAL && p->pre < NTK_PRE_NORMALIZE) return NTK_ERR_UNSUPPORTED;
+    if (n_bytes == 0) return NTK_OK;
+    if (!d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15)) return NTK_ERR_BAD_ARG;
+    KT_HIPCHK(hipSetDevice(t->device));
+    // chunks of kChunkBases; each chunk after the first is materialised from `halo` bytes before its start (a multiple of 16: d_seq
+    // stays aligned; >= k - 1: every window that ends in the chunk is whole), and only windows ending at or after the start count
+    const uint64_t halo = ((uint64_t)t->k - 1 + 15) & ~(uint64_t)15;
+    int rc = ensure_scratch(t, (n_bytes < kChunkBases ? n_bytes : kChunkBases) + (n_bytes > kChunkBases ? halo : 0));
+    if (rc) return rc;
+    for (uint64_t start = 0; start < n_bytes; start += kChunkBases) {
+        const uint64_t end = n_bytes - start > kChunkBases ? start + kChunkBases : n_bytes;
+        const uint64_t base = start ? start - halo : 0, len = end - base;
+        rc = ntk_materialize_device_quality(t->ctx, d_seq + base, d_qual ? d_qual + base : nullptr, len, p, t->d_values,
+                                            t->d_valid16, t->d_rc16);
+        if (rc) return rc;
+        KT_HIPCHK(hipSetDevice(t->device));
+        InsertArgs a;
+        a.values = t->d_values; a.valid16 = t->d_valid16;
+        a.first = start - base; a.n = len;
+        a.keys = t->d_keys; a.counts = t->d_counts; a.stats = t->d_stats;
+        a.mask = t->slots - 1; a.probe_max = t->probe_max;
+        hipLaunchKernelGGL(kt_insert_kernel, dim3(grid_for(len - a.first, kThreads, (unsigned)t->n_cu * 8)), dim3(kThreads), 0,
+                           t->stream, a);
+        KT_HIPCHK(hipGetLastError());
+    }
+    return NTK_OK;
+}
+
+int ntk_kmer_table_stats(ntk_kmer_table *t, struct ntk_kmer_table_stats *out)
+{
+    if (!t || !out) return NTK_ERR_BAD_ARG;
+    uint64_t w[kStWords];
+    int rc = read_stats(t, w);
+    if (rc) return rc;
+    out->n_distinct = w[kStDistinct] + (w[kStOnes] ? 1 : 0);
+    out->n_total = w[kStTotal];
+    out->n_dropped = w[kStDropped];
+    out->slots = t->slots; out->k = t->k; out->path = t->path;
+    return NTK_OK;
+}
+
+int ntk_kmer_table_extract_device(ntk_kmer_table *t, uint64_t min_count, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap, uint64_t *n)
+{
+    if (!t || !n) return NTK_ERR_BAD_ARG;
+    *n = 0;
+    uint64_t w[kStWords];
+    int rc = read_stats(t, w);
+    if (rc) return rc;
+    if (w[kStDropped]) return NTK_ERR_CAPACITY;
+    if (min_count == 0) min_count = 1;
+    const uint64_t nb = extract_blocks(t);
+    hipLaunchKernelGGL(kt_extract_count_kernel, dim3((unsigned)nb), dim3(kThreads), 0, t->stream, t->d_keys, t->d_counts, t->slots,
+                       min_count, t->d_block_counts);
+    KT_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(kt_extract_scan_kernel, dim3(1), dim3(1024), 0, t->stream, t->d_block_counts, (uint32_t)nb, t->d_offsets);
+    KT_HIPCHK(hipGetLastError());
+    KT_HIPCHK(hipMemcpyAsync(t->h_stage, t->d_offsets + nb, sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+    KT_HIPCHK(hipStreamSynchronize(t->stream));
+    const uint64_t in_table = t->h_stage[0], ones = w[kStOnes] >= min_count ? w[kStOnes] : 0;
+    const uint64_t need = in_table + (ones ? 1 : 0);
+    *n = need;
+    if (need > cap) return NTK_ERR_CAPACITY;
+    if (need == 0) return NTK_OK;
+    if (!d_keys || !d_counts) return NTK_ERR_BAD_ARG;
+    if (in_table) {
+        uint64_t *tk = nullptr, *tc = nullptr;
+        void *tmp = nullptr;
+        size_t tmp_bytes = 0;
+        hipError_t e;
+        if ((e = hipMalloc((void **)&tk, in_table * sizeof(uint64_t))) != hipSuccess ||
+            (e = hipMalloc((void **)&tc, in_table * sizeof(uint64_t))) != hipSuccess ||
+            (e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, tk, d_keys, tc, d_counts, in_table, 0u, 2 * t->k, t->stream)) != hipSuccess ||
+            (e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1)) != hipSuccess) {
+            rc = alloc_status(e);
+        } else {
+            hipLaunchKernelGGL(kt_extract_scatter_kernel, dim3((unsigned)nb), dim3(kThreads), 0, t->stream, t->d_keys, t->d_counts,
+                               t->slots, min_count, t->d_offsets, tk, tc);
+            e = hipGetLastError();
+            // the keys are < 4^k: a radix sort on the low 2k bits orders them
+            if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, tk, d_keys, tc, d_counts, in_table, 0u, 2 * t->k, t->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+            if (e != hipSuccess) { (void)hipGetLastError(); rc = NTK_ERR_HIP; }
+        }
+        (void)hipStreamSynchronize(t->stream);
+        for (void *q : {(void *)tk, (void *)tc, tmp})
+            if (q) (void)hipFree(q);
+        if (rc) return rc;
+    }
+    if (ones) {   // the all-ones key sorts last
+        t->h_stage[0] = kEmpty; t->h_stage[1] = ones;
+        KT_HIPCHK(hipMemcpyAsync(d_keys + in_table, t->h_stage, sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
+        KT_HIPCHK(hipMemcpyAsync(d_counts + in_table, t->h_stage + 1, sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
+        KT_HIPCHK(hipStreamSynchronize(t->stream));
+    }
+    return NTK_OK;
+}
+
+int ntk_kmer_table_spectrum(ntk_kmer_table *t, uint64_t *hist, uint32_t n_bins)
+{
+    if (!t || !hist || n_bins < 2 || n_bins > kMaxBins) return NTK_ERR_BAD_ARG;
+    uint64_t w[kStWords];
+    int rc = read_stats(t, w);
+    if (rc) return rc;
+    if (w[kStDropped]) return NTK_ERR_CAPACITY;
+    KT_HIPCHK(hipMemsetAsync(t->d_hist, 0, n_bins * sizeof(uint64_t), t->stream));
+    hipLaunchKernelGGL(kt_spectrum_kernel, dim3(grid_for(t->slots, kThreads, (unsigned)t->n_cu * 2)), dim3(kThreads),
+                       n_bins * sizeof(uint32_t), t->stream, t->d_keys, t->d_counts, t->slots, n_bins, t->d_hist);
+    KT_HIPCHK(hipGetLastError());
+    KT_HIPCHK(hipMemcpyAsync(t->h_stage, t->d_hist, n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+    KT_HIPCHK(hipStreamSynchronize(t->stream));
+    memcpy(hist, t->h_stage, n_bins * sizeof(uint64_t));
+    if (w[kStOnes]) hist[w[kStOnes] < n_bins - 1 ? w[kStOnes] : n_bins - 1]++;
+    return NTK_OK;
+}
+
+int ntk_kmer_table_lookup_device(ntk_kmer_table *t, const uint64_t *d_queries, uint64_t n, uint64_t *d_counts)
+{
+    if (!t || ((!d_queries || !d_counts) && n)) return NTK_ERR_BAD_ARG;
+    uint64_t w[kStWords];
+    int rc = read_stats(t, w);
+    if (rc) return rc;
+    if (w[kStDropped]) return NTK_ERR_CAPACITY;
+    if (n == 0) return NTK_OK;
+    hipLaunchKernelGGL(kt_lookup_kernel, dim3(grid_for(n, kThreads, (unsigned)t->n_cu * 8)), dim3(kThreads), 0, t->stream, t->d_keys,
+                       t->d_counts, t->slots - 1, t->probe_max, w[kStOnes], d_queries, n, d_counts);
+    KT_HIPCHK(hipGetLastError());
+    KT_HIPCHK(hipStreamSynchronize(t->stream));
+    return NTK_OK;
+}
+
+}  // extern "C"

@@ -58,6 +58,7 @@ extern "C" {
     pub fn ntk_ctx_create_on_stream(device: c_int, hip_stream: *mut c_void, out: *mut *mut NtkCtx) -> c_int;
     pub fn ntk_ctx_destroy(ctx: *mut NtkCtx);
     pub fn ntk_ctx_synchronize(ctx: *mut NtkCtx) -> c_int;
+    pub fn ntk_ctx_stream(ctx: *mut NtkCtx, device: *mut c_int, hip_stream: *mut *mut c_void) -> c_int;
     pub fn ntk_ctx_set_launch(ctx: *mut NtkCtx, blocks: c_int, threads_per_block: c_int) -> c_int;
     pub fn ntk_ctx_set_option(ctx: *mut NtkCtx, option: c_int, value: u64) -> c_int;
     pub fn ntk_ctx_get_option(ctx: *mut NtkCtx, option: c_int, value: *mut u64) -> c_int;

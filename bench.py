@@ -9,14 +9,17 @@ N > 1, the single RCCL all-reduce of the accumulators over xGMI (through the C A
     N > 1   configs[3]: 100 M reads in total, seed 0x5EED0004, record batches of 2^20 reads dealt round-robin to the
             GPUs (record i -> GPU (i / 2^20) mod N); every GPU keeps its shard resident     ("strong")
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
         N > 1 without a torch.distributed environment re-launches itself as
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...
         (one process per GPU); launched that way by the driver it runs as is.
 
-Rank 0 prints ONE JSON line: metric/value/unit/... + "roofline" + "cpu_baseline" + "secondary" (N = 1).
-Before anything is timed every rank compares its WHOLE shard bit-exactly with the oracle (all five scalars and the
-4096 bins); after timing, the all-reduced result is compared with the sum of the ranks' oracle results.
+Rank 0 prints ONE JSON line: metric/value/unit/... + "roofline" (from the hipEvents of the timed steps) + "cpu_baseline".
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds the rest: before anything is timed every rank compares its WHOLE shard bit-exactly with the oracle (all five
+scalars and the 4096 bins), and after timing the all-reduced result is compared with the sum of the ranks' oracle results;
+at N = 1 also the rocprofv3 --pmc counter passes (roofline.traffic, roofline.valu), "cpu_baseline" and "secondary".
+(--no-verify, --no-pmc, --no-cpu-baseline and --no-secondary leave a part out of a --full run.)
 """
 import argparse
 import collections
@@ -785,9 +788,9 @@ def pmc_passes(args, n_bytes):
     tool = shutil.which("rocprofv3")
     if not tool:
         return {}
-    env = dict(os.environ, NTK_BENCH_PMC_CHILD="1", TMPDIR="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "1", "--preheat-ms", "5", "--no-verify", "--no-cpu-baseline",
-             "--no-secondary", "--no-pmc", "--reads", str(args.reads or 10_000_000), "--read-len", str(args.read_len), "--k", str(args.k),
+    env = dict(os.environ, TMPDIR="/tmp")
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "1", "--preheat-ms", "5",   # a plain run: no --full
+             "--reads", str(args.reads or 10_000_000), "--read-len", str(args.read_len), "--k", str(args.k),
              "--n-per-1024", str(args.n_per_1024), "--blocks", str(args.blocks), "--threads", str(args.threads)]
     got, names = {}, collections.Counter()
     for counters in (["FETCH_SIZE"], ["WRITE_SIZE"], ["SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_ACTIVE_INST_VALU", "SQ_ACTIVE_INST_VALU2", "GRBM_GUI_ACTIVE"]):
@@ -916,6 +919,9 @@ def main():
     ap.add_argument("--n-per-1024", type=int, default=1)
     ap.add_argument("--blocks", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="threads per block (0 = the library's choice)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the whole-shard oracle check, and at N = 1 the rocprofv3 --pmc "
+                         "passes, cpu_baseline and secondary (a plain run skips them all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=24.0)
     ap.add_argument("--cpu-reference-bin", default=os.environ.get("NTK_CPU_REFERENCE_BIN"),
@@ -942,6 +948,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_verify = args.no_pmc = args.no_cpu_baseline = args.no_secondary = True
 
     if args.gpus > 1 and "RANK" not in os.environ:
         if not args.single_device:
@@ -1168,7 +1176,7 @@ def main():
 
     traffic, traffic_source = args.traffic_bytes, ("--traffic-bytes" if args.traffic_bytes is not None else None)
     pmc = {}
-    if world == 1 and rank == 0 and not args.no_pmc and not os.environ.get("NTK_BENCH_PMC_CHILD"):
+    if world == 1 and rank == 0 and not args.no_pmc:
         # measured in THIS run: three separate rocprofv3 --pmc passes (FETCH_SIZE; WRITE_SIZE; the SQ / GRBM counters) over short child
         # runs of this same command, per launch of the scan kernel, corrected as MI355X_MICROARCH.md prescribes for gfx950
         pmc = pmc_passes(args, n_bytes)

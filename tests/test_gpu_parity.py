@@ -1574,7 +1574,7 @@ def test_bench_self_launch_all_devices(tmp_path):
     n_dev = torch.cuda.device_count()
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n_dev), "--reads", "8000000", "--steps", "3", "--warmup", "1",
-           "--preheat-ms", "20", "--no-cpu-baseline", "--no-secondary", "--init-timeout-s", "120", "--dump-outputs", str(tmp_path / "out")]
+           "--preheat-ms", "20", "--full", "--no-cpu-baseline", "--no-secondary", "--init-timeout-s", "120", "--dump-outputs", str(tmp_path / "out")]
     if n_dev == 1:   # one rank: the RCCL path needs the rank environment (--gpus 1 alone is the single-GPU configs[1] run)
         env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
         cmd += ["--workload", "c4"]
@@ -1609,6 +1609,30 @@ def test_bench_collective_fallback_is_opt_in():
     assert r.returncode == 0, r.stderr[-2000:]
     cfg = json.loads(r.stdout.strip().splitlines()[-1])["config"]
     assert cfg["rccl_ranks"] == 0 and cfg["collective"].startswith("FALLBACK")
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """`python bench.py --gpus 1` without --full runs no oracle check, counter pass, cpu_baseline or secondary, so the result of its
+    last timed step is checked here instead: the dumped arrays against the oracle on the same configs[1] reads."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k_: v for k_, v in os.environ.items() if k_ not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    n_reads = 1_000_000
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--reads", str(n_reads), "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["unit"] == "Gbases/s" and line["higher_is_better"] and line["dtype"] == "u64" and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["result"]["verified"] is None and line["cpu_baseline"] is None and "secondary" not in line
+    assert not (line["roofline"]["traffic_source"] or "").startswith("measured in this run")   # no rocprofv3 --pmc child pass
+    want = O.reduce_fused_parallel(O.synth_reads(0x5EED0002, 0, n_reads, 150, 1), 151, 21, True, True, True, max(1, os.cpu_count() or 1))
+    counts, digests = np.load(tmp_path / "out" / "counts.npy"), np.load(tmp_path / "out" / "digests.npy")
+    assert [int(v) for v in counts] == [want["n_total"], want["n_fwd"], want["n_rc"]]
+    assert [sum(int(w) << s for w, s in zip(row, (48, 32, 16, 0))) for row in digests] == [want["sum"], want["xor"]]
+    assert np.array_equal(np.load(tmp_path / "out" / "hist.npy").astype(np.uint64), np.asarray(want["hist"], dtype=np.uint64))
 
 
 @pytest.mark.parametrize("chunk_bytes", [None, 97, 4096])

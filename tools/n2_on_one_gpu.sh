@@ -4,8 +4,8 @@
 set -e
 R=${READS:-3000000}   # total reads: > 2^20, so that both ranks own batches
 # (plain `python bench.py --gpus 2` spawns its own two ranks; config 4: seed 0x5EED0004, batches of 2^20 reads round-robin)
-python bench.py --gpus 2 --steps 5 --warmup 2 --reads $R --backend gloo --single-device 2>/dev/null | tail -1 > ${TMPDIR:-/tmp}/ntk_n2.json
-python bench.py --workload c4 --steps 2 --warmup 1 --reads $R --no-cpu-baseline --no-secondary | tail -1 > ${TMPDIR:-/tmp}/ntk_n1.json
+python bench.py --gpus 2 --steps 5 --warmup 2 --reads $R --backend gloo --single-device --full 2>/dev/null | tail -1 > ${TMPDIR:-/tmp}/ntk_n2.json
+python bench.py --workload c4 --steps 2 --warmup 1 --reads $R --full --no-cpu-baseline --no-secondary | tail -1 > ${TMPDIR:-/tmp}/ntk_n1.json
 python - <<'PY'
 import json, os
 a, b = json.load(open(os.path.join(os.environ.get("TMPDIR", "/tmp"), "ntk_n2.json"))), json.load(open(os.path.join(os.environ.get("TMPDIR", "/tmp"), "ntk_n1.json")))

@@ -52,7 +52,8 @@ int ntk_kmer_table_count_device(ntk_kmer_table *t, const uint8_t *d_seq, const u
 int ntk_kmer_table_stats(ntk_kmer_table *t, struct ntk_kmer_table_stats *out);
 /* The pairs with count >= min_count (0 counts as 1), keys ascending, into device arrays of `cap` entries; *n = the number of pairs.
  * cap too small: NTK_ERR_CAPACITY with *n = the number needed (d_keys / d_counts may be NULL with cap 0 to ask for it).
- * Extract, spectrum and lookup return NTK_ERR_CAPACITY when n_dropped > 0: an incomplete table never reads as a complete one. */
+ * Extract, spectrum and lookup return NTK_ERR_CAPACITY when n_dropped > 0 (extract with *n = 0): an incomplete table never reads as
+ * a complete one. */
 int ntk_kmer_table_extract_device(ntk_kmer_table *t, uint64_t min_count, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap,
                                   uint64_t *n);
 /* Host array hist[n_bins], n_bins = 2..16384: hist[c] = distinct keys with count c for 1 <= c < n_bins - 1, hist[n_bins - 1] =

@@ -6,14 +6,17 @@ import re
 import subprocess
 import tempfile
 
+import numpy as np
 import pytest
 
 import _builds as B
+import _count_model as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "needletail_amd", "libneedletail_amd_count.so")
 CORE = os.path.join(ROOT, "needletail_amd", "libneedletail_amd.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_count.h")
+HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_count.hip")
 
 # every kernel of the count library with the test that launches it (file, test function); rocPRIM's sort kernels by namespace
 COUNT_KERNELS = {
@@ -100,3 +103,77 @@ def test_no_device_is_a_loud_error():
     with pytest.raises(nt.NtkError) as e:
         nt.KmerTable(21, nt.PATH_BITS_CANONICAL, 1000)
     assert e.value.status == 4   # NTK_ERR_NO_DEVICE
+
+
+# ---- the host model of the table (tests/_count_model.py), which the edge tests aim with --------------------------------------
+
+def _fmix64_int(x):
+    x ^= x >> 33
+    x = x * 0xff51afd7ed558ccd & M.M64
+    x ^= x >> 33
+    x = x * 0xc4ceb9fe1a85ec53 & M.M64
+    return x ^ (x >> 33)
+
+
+def test_model_fmix64_and_its_inverse():
+    rng = np.random.default_rng(0xF3)
+    x = rng.integers(0, 1 << 64, 200_000, dtype=np.uint64)
+    x[:4] = [0, 1, M.M64, 1 << 63]
+    assert np.array_equal(M.fmix64_inv(M.fmix64(x)), x) and np.array_equal(M.fmix64(M.fmix64_inv(x)), x)
+    assert [int(v) for v in M.fmix64(x[:64])] == [_fmix64_int(int(v)) for v in x[:64]]
+    assert all(m * i & M.M64 == 1 for m, i in zip(M.FMIX_MUL, M.FMIX_INV))
+
+
+def test_model_revcomp_is_the_oracles():
+    import oracle as O
+    rng = np.random.default_rng(0xF4)
+    for k in (1, 2, 13, 16, 31, 32):
+        v = rng.integers(0, 1 << (2 * k), 64, dtype=np.uint64)
+        assert [int(r) for r in M.revcomp(v, k)] == [O.bit_reverse_complement(int(a), k) for a in v], k
+
+
+@pytest.mark.parametrize("k,canonical", [(32, False), (32, True), (16, False), (16, True), (13, False)])
+def test_model_keys_with_home(k, canonical):
+    slots = 8192
+    for h in (0, 1000, slots - 7, slots - 1):
+        keys = M.keys_with_home(h, slots, k, 120, canonical)
+        assert keys.size == 120 and np.unique(keys).size == 120
+        assert (M.home(keys, slots) == h).all()
+        assert (keys != np.uint64(M.EMPTY)).all()
+        if k < 32:
+            assert (keys < np.uint64(1 << (2 * k))).all()
+        if canonical:
+            assert (keys <= M.revcomp(keys, k)).all()
+        assert np.array_equal(M.keys_with_home(h, slots, k, 30, canonical), keys[:30])   # a shorter list is a prefix
+
+
+def test_model_records_emit_exactly_the_keys():
+    import oracle as O
+    keys = np.array([0, 5, (1 << 42) - 1, 12345678], dtype=np.uint64)
+    buf = M.records_for(keys, [3, 1, 2, 7], 21, seed=1)
+    assert len(buf) == 13 * 22
+    got = np.unique(O.bit_kmers_arrays(buf, 21, False)[1], return_counts=True)
+    assert np.array_equal(got[0], np.sort(keys)) and list(got[1]) == [3, 1, 7, 2]
+
+
+def test_model_sizing_rule():
+    assert [M.slots_for(c) for c in (1, 2, 3, 4, 6, 7, 12, 13)] == [2, 4, 4, 8, 8, 16, 16, 32]
+    for j in range(1, 37):
+        assert M.slots_for(3 << j) == 4 << j and M.slots_for((3 << j) + 1) == 8 << j
+
+
+def test_table_hash_probe_bound_and_chunk_are_the_models():
+    """The edge tests aim keys at home slots and records at chunk seams with tests/_count_model.py.  If the table's hash, probe
+    bound or chunk length changes, say so here, on the CPU, rather than as a puzzling count mismatch on the GPU."""
+    src = open(HIP).read()
+    m = re.search(r"inline uint64_t fmix64\(uint64_t x\)\s*\{(.*?)\}", src, re.S)
+    assert m, "fmix64 not found in ntk_count.hip"
+    steps = re.findall(r"x \^= x >> (\d+);|x \*= (0x[0-9a-fA-F]+)ull;", m.group(1))
+    got = [int(a) if a else int(b, 16) for a, b in steps]
+    want = [M.FMIX_SHIFT, M.FMIX_MUL[0], M.FMIX_SHIFT, M.FMIX_MUL[1], M.FMIX_SHIFT]
+    assert got == want, f"ntk_count.hip's fmix64 is {got}, tests/_count_model.py's is {want}: update the model with the hash"
+    assert re.search(r"fmix64\(key\) & a\.mask", src) and re.search(r"fmix64\(q\) & mask", src), "home slot is not fmix64 & mask"
+    assert len(re.findall(r"slot = \(slot \+ 1\) & (?:a\.)?mask", src)) == 2, "probing is not linear with wrap-around"
+    assert int(re.search(r"kProbeMax = (\d+);", src).group(1)) == M.PROBE_MAX
+    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", src)
+    assert int(chunk.group(1)) << int(chunk.group(2)) == M.CHUNK

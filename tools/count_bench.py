@@ -2,7 +2,10 @@
 
   (a) config2: the config-2 batch (10M x 150 bp synthetic reads, k = 21, byte path after normalize): ~1.3 G nearly all-distinct keys in
       a 2^31-slot table (32 GiB);
-  (b) genome: reads sampled error-free from a seeded random 1 Mb genome, ~1.5 Gbases (~1500x coverage): a repetitive key stream.
+  (b) genome: reads sampled error-free from a seeded random 1 Mb genome, ~1.5 Gbases (~1500x coverage): a repetitive key stream;
+  (c) hotkey (--only hotkey): one record of 2^30 A at k = 21 (canonical bits path): 2^30 - 20 occurrences of one key, every lane
+      adding to one table slot; one timed call after a 64 MiB warm-up, no repetition.  Then the same with T at k = 32 on the forward
+      bits path: the all-ones key, counted in the side word.
 
 For each: count (materialise + insert) in Gbases/s and inserted k-mers/s, extract (count, scan, scatter, sort) and spectrum in ms.
 Prints one JSON line per workload.  --quick: one repetition, for a kernel-trace run (rocprofv3 --kernel-trace --stats -- python ...)."""
@@ -18,7 +21,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import needletail_amd as nt  # noqa: E402
-from test_gpu_count import device_items  # noqa: E402
+from _count_helpers import device_items  # noqa: E402
 
 
 def genome_reads(dev: torch.Tensor, seed: int, genome_len: int, n_reads: int, L: int):
@@ -67,14 +70,42 @@ def run(ctx, name, dev, nbytes, k, path, pre, capacity, reps):
             "extract_ms": round(min(extract_ms), 3), "spectrum_ms": round(min(spectrum_ms), 3)}
 
 
+def hotkey(ctx, dev, nbytes, base, k, path):
+    stream = torch.cuda.current_stream()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    dev.fill_(ord("\n"))
+    dev[: nbytes - 1] = base
+    torch.cuda.synchronize()
+    with nt.KmerTable(k, path, 1024, ctx) as t:
+        t.count_device(dev, (64 << 20) + 16, nt.PRE_NONE)   # warm-up: kernels loaded, the scratch of a whole chunk allocated
+        ctx.synchronize()
+        t.reset()
+        ev[0].record(stream)
+        t.count_device(dev, nbytes, nt.PRE_NONE)
+        ev[1].record(stream)
+        ev[1].synchronize()
+        st = t.stats()
+    ms = ev[0].elapsed_time(ev[1])
+    return {"workload": "hotkey" if path != nt.PATH_BITS else "hotkey_side_word", "k": k, "bases": nbytes - 1,
+            "n_total": st["n_total"], "n_distinct": st["n_distinct"], "n_dropped": st["n_dropped"], "count_ms": round(ms, 3),
+            "inserted_kmers_per_s": round(st["n_total"] / ms * 1e3, 1), "s_per_2_32_occurrences": round((1 << 32) / st["n_total"] * ms / 1e3, 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", choices=["config2", "genome"], default=None)
+    ap.add_argument("--only", choices=["config2", "genome", "hotkey"], default=None)
     a = ap.parse_args()
     reps = 1 if a.quick else a.reps
     ctx = nt.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    if a.only == "hotkey":
+        nbytes = (1 << 30) + 1
+        dev = torch.empty(nbytes + 1024, dtype=torch.uint8, device="cuda")
+        print(json.dumps(hotkey(ctx, dev, nbytes, ord("A"), 21, nt.PATH_BITS_CANONICAL)), flush=True)
+        print(json.dumps(hotkey(ctx, dev, nbytes, ord("T"), 32, nt.PATH_BITS)), flush=True)
+        ctx.close()
+        return
     L = 150
     n_reads = 10_000_000
     nbytes = n_reads * (L + 1)

@@ -1,12 +1,14 @@
-// count_kmers: exact canonical k-mer counts of a FASTA / FASTQ file on the GPU (include/needletail_amd_count.h).
+// count_kmers: exact canonical k-mer counts of a FASTA / FASTQ file on the GPU (include/needletail_amd_count.h; k = 33..63 on the byte
+// path: include/needletail_amd_wide_count.h).
 //
 //   count_kmers [-k K] [-m MIN] [-s BINS] [-p bytes|bits|canonical] [-c CAPACITY] FILE
 //
 // Prints `kmer<TAB>count` for every k-mer seen at least MIN times (default 1), k-mers ascending, or with -s the abundance spectrum
 // (`count<TAB>distinct k-mers`, the last line: BINS - 1 times or more).  Path `bytes` (default) is the reference README's chain,
 // normalize(false) -> canonical_kmers(k, &rc); `bits` / `canonical` are strip_returns -> bit_kmers(k, false / true).  The records go
-// through the reader (ntk_reader_*) and the batch packer (ntk_batch_append), the counting loop is the device table.
-#include "needletail_amd_count.h"
+// through the reader (ntk_reader_*) and the batch packer (ntk_batch_append), the counting loop is the device table: the count table for
+// k <= 32, the wide table for k = 33..63 (byte path only; the bit paths stop at k = 32 and exit non-zero above it).
+#include "needletail_amd_wide_count.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -61,8 +63,13 @@ int main(int argc, char **argv)
     if ((rc = ntk_ctx_create(0, &ctx))) return fail("device", rc);
     if (!capacity) capacity = bases ? bases : 1;   // distinct k-mers never exceed the windows
     if (k < 32 && capacity > ((uint64_t)1 << (2 * k))) capacity = (uint64_t)1 << (2 * k);
+    // k = 33..63 on the byte path: the wide table, whose keys are two words {hi, lo}
+    const bool wide = k > 32 && path == NTK_PATH_BYTES_CANONICAL;
     ntk_kmer_table *t = nullptr;
-    if ((rc = ntk_kmer_table_create(ctx, k, path, capacity, &t))) return fail("table", rc);
+    ntk_wide_table *wt = nullptr;
+    if ((rc = wide ? ntk_wide_table_create(ctx, k, path, capacity, &wt) : ntk_kmer_table_create(ctx, k, path, capacity, &t)))
+        return fail("table", rc);
+    const uint32_t words = wide ? 2 : 1;   // u64 words per key
 
     // pack with ntk_batch_append (the pre-step's deleted bytes out, one break byte per record), upload, count
     const uint64_t batch_bytes = (uint64_t)256 << 20;
@@ -80,7 +87,8 @@ int main(int argc, char **argv)
         if ((rc = ntk_batch_buffers(b, &h_seq, &offs, &n_bytes, &n_records))) return fail("batch", rc);
         if (n_records == 0) return fail("record larger than a batch", NTK_ERR_CAPACITY);
         if (hipMemcpy(d_seq, h_seq, n_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail("upload", NTK_ERR_HIP);
-        if ((rc = ntk_kmer_table_count_device(t, d_seq, nullptr, n_bytes, &p))) return fail("count", rc);
+        if ((rc = wide ? ntk_wide_table_count_device(wt, d_seq, nullptr, n_bytes, &p) : ntk_kmer_table_count_device(t, d_seq, nullptr, n_bytes, &p)))
+            return fail("count", rc);
         if ((rc = ntk_ctx_synchronize(ctx))) return fail("count", rc);
         ntk_batch_release(ctx, b);
         if ((rc = ntk_batch_acquire(ctx, batch_bytes, 1u << 22, &b))) return fail("batch", rc);
@@ -89,29 +97,37 @@ int main(int argc, char **argv)
 
     if (bins) {
         std::vector<uint64_t> hist(bins);
-        if ((rc = ntk_kmer_table_spectrum(t, hist.data(), bins))) return fail("spectrum", rc);
+        if ((rc = wide ? ntk_wide_table_spectrum(wt, hist.data(), bins) : ntk_kmer_table_spectrum(t, hist.data(), bins))) return fail("spectrum", rc);
         for (uint32_t c = 1; c < bins; c++) printf("%u\t%llu\n", c, (unsigned long long)hist[c]);
     } else {
         uint64_t n = 0;
-        rc = ntk_kmer_table_extract_device(t, min_count, nullptr, nullptr, 0, &n);
+        rc = wide ? ntk_wide_table_extract_device(wt, min_count, nullptr, nullptr, 0, &n)
+                  : ntk_kmer_table_extract_device(t, min_count, nullptr, nullptr, 0, &n);
         if (rc && !(rc == NTK_ERR_CAPACITY && n)) return fail("extract", rc);
-        std::vector<uint64_t> keys(n), counts(n);
+        std::vector<uint64_t> keys(n * words), counts(n);
         uint64_t *dk = nullptr, *dc = nullptr;
         if (n) {
-            if (hipMalloc((void **)&dk, n * 8) != hipSuccess || hipMalloc((void **)&dc, n * 8) != hipSuccess) return fail("device buffer", NTK_ERR_HIP);
-            if ((rc = ntk_kmer_table_extract_device(t, min_count, dk, dc, n, &n))) return fail("extract", rc);
-            if (hipMemcpy(keys.data(), dk, n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            if (hipMalloc((void **)&dk, n * 8 * words) != hipSuccess || hipMalloc((void **)&dc, n * 8) != hipSuccess) return fail("device buffer", NTK_ERR_HIP);
+            if ((rc = wide ? ntk_wide_table_extract_device(wt, min_count, dk, dc, n, &n) : ntk_kmer_table_extract_device(t, min_count, dk, dc, n, &n)))
+                return fail("extract", rc);
+            if (hipMemcpy(keys.data(), dk, n * 8 * words, hipMemcpyDeviceToHost) != hipSuccess ||
                 hipMemcpy(counts.data(), dc, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail("download", NTK_ERR_HIP);
             (void)hipFree(dk); (void)hipFree(dc);
         }
         std::string kmer(k, 'A');
         for (uint64_t j = 0; j < n; j++) {
-            for (uint32_t c = 0; c < k; c++) kmer[c] = "ACGT"[(keys[j] >> (2 * (k - 1 - c))) & 3];
+            if (wide) {   // {hi, lo}: the first k - 32 bases, then the last 32
+                for (uint32_t c = 0; c < k - 32; c++) kmer[c] = "ACGT"[(keys[2 * j] >> (2 * (k - 33 - c))) & 3];
+                for (uint32_t c = 0; c < 32; c++) kmer[k - 32 + c] = "ACGT"[(keys[2 * j + 1] >> (2 * (31 - c))) & 3];
+            } else {
+                for (uint32_t c = 0; c < k; c++) kmer[c] = "ACGT"[(keys[j] >> (2 * (k - 1 - c))) & 3];
+            }
             printf("%s\t%llu\n", kmer.c_str(), (unsigned long long)counts[j]);
         }
     }
     (void)hipFree(d_seq);
     ntk_kmer_table_destroy(t);
+    ntk_wide_table_destroy(wt);
     ntk_ctx_destroy(ctx);
     return 0;
 }

@@ -8,7 +8,10 @@
       bits path: the all-ones key, counted in the side word.
 
 For each: count (materialise + insert) in Gbases/s and inserted k-mers/s, extract (count, scan, scatter, sort) and spectrum in ms.
-Prints one JSON line per workload.  --quick: one repetition, for a kernel-trace run (rocprofv3 --kernel-trace --stats -- python ...)."""
+Prints one JSON line per workload.  --quick: one repetition, for a kernel-trace run (rocprofv3 --kernel-trace --stats -- python ...).
+
+--k K runs (a) and (b) at that k instead of 21; k >= 33 selects the wide table (include/needletail_amd_wide_count.h, k = 33..63), whose
+count is one fused kernel (read + insert) and whose extract sorts {hi, lo} pairs."""
 import argparse
 import json
 import os
@@ -22,6 +25,21 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import needletail_amd as nt  # noqa: E402
 from _count_helpers import device_items  # noqa: E402
+from needletail_amd import wide_counting  # noqa: E402
+
+
+def wide_device_items(table, min_count=1):
+    """(keys [n, 2], counts) of a wide table as device tensors."""
+    import ctypes as C
+    lib = wide_counting.lib()
+    n = C.c_uint64(0)
+    lib.ntk_wide_table_extract_device(table._h, min_count, None, None, 0, C.byref(n))
+    keys = torch.empty(max(2 * n.value, 2), dtype=torch.int64, device="cuda")
+    counts = torch.empty(max(n.value, 1), dtype=torch.int64, device="cuda")
+    rc = lib.ntk_wide_table_extract_device(table._h, min_count, C.c_void_p(keys.data_ptr()), C.c_void_p(counts.data_ptr()), n.value,
+                                           C.byref(n))
+    assert rc == 0, rc
+    return keys, counts
 
 
 def genome_reads(dev: torch.Tensor, seed: int, genome_len: int, n_reads: int, L: int):
@@ -42,7 +60,9 @@ def run(ctx, name, dev, nbytes, k, path, pre, capacity, reps):
     stream = torch.cuda.current_stream()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
     count_ms, extract_ms, spectrum_ms = [], [], []
-    with nt.KmerTable(k, path, capacity, ctx) as t:
+    wide = k > 32
+    table, items = (nt.WideKmerTable, wide_device_items) if wide else (nt.KmerTable, device_items)
+    with table(k, path, capacity, ctx) as t:
         for r in range(reps + 1):   # the first repetition warms up
             t.reset()
             ev[0].record(stream)
@@ -50,7 +70,7 @@ def run(ctx, name, dev, nbytes, k, path, pre, capacity, reps):
             ev[1].record(stream)
             ev[1].synchronize()
             ev[2].record(stream)
-            keys, counts = device_items(t)
+            keys, counts = items(t)
             ev[3].record(stream)
             ev[3].synchronize()
             del keys, counts
@@ -64,7 +84,7 @@ def run(ctx, name, dev, nbytes, k, path, pre, capacity, reps):
                 spectrum_ms.append(ev[4].elapsed_time(ev[5]))
         st = t.stats()
     best = min(count_ms)
-    return {"workload": name, "k": k, "bases": nbytes, "slots": st["slots"], "n_total": st["n_total"], "n_distinct": st["n_distinct"],
+    return {"workload": name, "table": "wide" if wide else "narrow", "k": k, "bases": nbytes, "slots": st["slots"], "n_total": st["n_total"], "n_distinct": st["n_distinct"],
             "n_dropped": st["n_dropped"], "count_ms": round(best, 3), "count_ms_all": [round(x, 3) for x in count_ms],
             "gbases_per_s": round(nbytes / best / 1e6, 3), "inserted_kmers_per_s": round(st["n_total"] / best * 1e3, 1),
             "extract_ms": round(min(extract_ms), 3), "spectrum_ms": round(min(spectrum_ms), 3)}
@@ -96,6 +116,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--only", choices=["config2", "genome", "hotkey"], default=None)
+    ap.add_argument("--k", type=int, default=21, help="k of workloads (a) and (b); k >= 33: the wide table")
     a = ap.parse_args()
     reps = 1 if a.quick else a.reps
     ctx = nt.Context(0, stream=torch.cuda.current_stream().cuda_stream)
@@ -112,11 +133,11 @@ def main():
     dev = torch.empty(nbytes + 1024, dtype=torch.uint8, device="cuda")
     if a.only in (None, "config2"):
         ctx.synth_reads_device(0x5EED0002, 0, n_reads, L, 1, dev)
-        print(json.dumps(run(ctx, "config2", dev, nbytes, 21, nt.PATH_BYTES_CANONICAL, nt.PRE_NORMALIZE, 1_400_000_000, reps)), flush=True)
+        print(json.dumps(run(ctx, "config2", dev, nbytes, a.k, nt.PATH_BYTES_CANONICAL, nt.PRE_NORMALIZE, 1_400_000_000, reps)), flush=True)
     if a.only in (None, "genome"):
         genome_reads(dev, 0x6E0E, 1_000_000, n_reads, L)
         torch.cuda.synchronize()
-        print(json.dumps(run(ctx, "genome", dev, nbytes, 21, nt.PATH_BYTES_CANONICAL, nt.PRE_NORMALIZE, 2_000_000, reps)), flush=True)
+        print(json.dumps(run(ctx, "genome", dev, nbytes, a.k, nt.PATH_BYTES_CANONICAL, nt.PRE_NORMALIZE, 2_000_000, reps)), flush=True)
     ctx.close()
 
 

@@ -220,17 +220,15 @@ int resolve_mode(const ntk_params *p, bool batch_face, Mode *m)
 // (2.45 ms per 1.51 GB of input against 2.45-2.50 ms, profiles/r04b/wbw.txt), i.e. it is bound by the 8 bytes it writes per position.
 constexpr int kMaxShards = 256;      // work counters: the pull atomics of > 6000 waves on 8 counters were the bottleneck (profiles/r02)
 constexpr uint32_t kLowerRing = 64;  // "a lower-case byte was seen" flags of consecutive speculative launches (each launch clears its successor's)
+// a launch of a tile scan covers at most this many tiles, a shard <= 2^22 of them, so that the per-block u32 histogram cells (a block can at
+// most drain its whole shard: 2^22 * 992 windows), the u32 work counters and 32-bit buffer offsets cannot overflow
+constexpr uint64_t kMaxTilesPerLaunch = (uint64_t)8 << 22;
 
-template <bool REDUCE, bool QM>
-const void *pick_scan(const Mode &m, uint32_t k)
+// The round-1 scan_kernel, materialise mode only (QM names a template argument).
+// (no TIE_RC && !ACCEPT_U build: that is the byte path on input that was not normalised, which materialise mode rejects - run_scan)
+template <bool QM>
+const void *pick_materialise(const Mode &m, uint32_t k)
 {
-    // reduce mode: every (path, k, quality) has an sv2 build; the kernel lives in its own translation unit (ntk_scan2.hip, built
-    // with the ILP-driven iterative scheduler).  The round-1 kernel below serves materialise mode only.
-    if constexpr (REDUCE) {
-        if (QM) return ntk_pick_scan2_q((int)k, m.canon, m.tie_rc, m.accept_u);
-        return m.canon ? ntk_pick_scan2((int)k, m.tie_rc, m.accept_u) : ntk_pick_scan2_fwd((int)k, m.accept_u);
-    } else {
-        // (no TIE_RC && !ACCEPT_U build: that is the byte path on input that was not normalised, which materialise mode rejects - run_scan)
 #define NTK_PICK_FIX(KF, T, U)                                                                      \
     if (!QM && m.kw == 2 && m.canon && k == KF && m.tie_rc == T && m.accept_u == U)                  \
         return (const void *)&scan_kernel<2, true, T, U, false, KF>;
@@ -247,7 +245,15 @@ const void *pick_scan(const Mode &m, uint32_t k)
     NTK_PICK(2, true, true, true)
 #undef NTK_PICK
     return nullptr;
-    }
+}
+
+// reduce mode: every (path, k, quality) has an sv2 build; the kernel lives in its own translation unit (ntk_scan2.hip, built
+// with the ILP-driven iterative scheduler).
+const void *pick_scan(const Mode &m, uint32_t k, bool reduce, bool quality)
+{
+    if (!reduce) return quality ? pick_materialise<true>(m, k) : pick_materialise<false>(m, k);
+    if (quality) return ntk_pick_scan2_q((int)k, m.canon, m.tie_rc, m.accept_u);
+    return m.canon ? ntk_pick_scan2((int)k, m.tie_rc, m.accept_u) : ntk_pick_scan2_fwd((int)k, m.accept_u);
 }
 
 // Fused windowed-minimizer builds of the sv2 kernel (ntk_tile.hpp lane_tile_sv2_min): k = 15..23 x w = 5, 9..12 (windows of up to 34 bytes),
@@ -267,121 +273,236 @@ int get_event(ntk_ctx *c, hipEvent_t *e)
     return NTK_OK;
 }
 
-// CanonicalKmers over raw (un-normalised) bytes into the accumulators: canonical_bytes_reduce_kernel + fold (ntk_kernels.hpp).
-int raw_bytes_blocks(const ntk_ctx *c, uint64_t n)
+// What every reduce / materialise launch is made of.  A timed span on c->stream (ntk_ctx_enable_timing; a no-op without it): begin() takes an
+// event pair from the pool and records the start, end() records the stop and files the pair in `used`.  A span that does not get that far -
+// any error return on the way - hands both events back to the pool when it goes out of scope.
+struct TimedSpan {
+    ntk_ctx *c = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    TimedSpan() = default;
+    TimedSpan(const TimedSpan &) = delete;
+    TimedSpan &operator=(const TimedSpan &) = delete;
+    ~TimedSpan() { for (hipEvent_t e : {e0, e1}) if (e) c->ev_free.push_back(e); }
+    int begin(ntk_ctx *ctx)
+    {
+        if (!ctx->timing) return NTK_OK;
+        c = ctx;
+        int rc = get_event(c, &e0);
+        if (!rc) rc = get_event(c, &e1);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(e0, c->stream));
+        return NTK_OK;
+    }
+    int end(std::vector<std::pair<hipEvent_t, hipEvent_t>> &used)
+    {
+        if (!e0) return NTK_OK;
+        HIPCHK(hipEventRecord(e1, c->stream));
+        used.emplace_back(e0, e1);
+        e0 = e1 = nullptr;
+        return NTK_OK;
+    }
+};
+
+// the blocks a launch may use: what ntk_ctx_set_launch forces, else per_cu on every CU
+inline uint64_t block_cap(const ntk_ctx *c, int per_cu) { return c->launch_blocks > 0 ? (uint64_t)c->launch_blocks : (uint64_t)c->n_cu * per_cu; }
+inline int blocks_for(const ntk_ctx *c, uint64_t n, uint64_t tile, int per_cu)   // one block per tile of input, up to the cap
 {
-    const uint64_t tile = (uint64_t)kPlThreads * 32;   // (canonical_bytes_reduce_kernel: 32 starts per thread)
-    const uint64_t n_tiles = (n + tile - 1) / tile;
-    const uint64_t max_blocks = c->launch_blocks > 0 ? (uint64_t)c->launch_blocks : (uint64_t)c->n_cu * 8;
-    return (int)(n_tiles < max_blocks ? n_tiles : max_blocks);
+    const uint64_t n_tiles = (n + tile - 1) / tile, cap = block_cap(c, per_cu);
+    return (int)(n_tiles < cap ? n_tiles : cap);
 }
+
+// resident blocks per CU of build fn at a block size, clamped to 1..cap; asked once per (fn, threads)
+int resident_blocks(ntk_ctx *c, const void *fn, int threads, size_t lds, int cap, int *per_cu)
+{
+    const auto key = std::make_pair(fn, threads);
+    auto it = c->occupancy.find(key);
+    if (it != c->occupancy.end()) { *per_cu = it->second; return NTK_OK; }
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, threads, lds));
+    *per_cu = *per_cu < 1 ? 1 : (*per_cu > cap ? cap : *per_cu);
+    c->occupancy[key] = *per_cu;
+    return NTK_OK;
+}
+
+// the flag word of a speculative launch and its successor's, which the launch clears (the ring of kLowerRing words behind the work counters)
+struct FlagPair { uint32_t *flag = nullptr, *next = nullptr; };
+inline FlagPair next_flag(ntk_ctx *c)
+{
+    FlagPair f;
+    f.flag = c->d_lower + c->lower_idx;
+    c->lower_idx = (c->lower_idx + 1) % kLowerRing;
+    f.next = c->d_lower + c->lower_idx;
+    return f;
+}
+
+// fold_kernel over `rows` rows of the ctx partials into the ctx accumulators (same stream, behind the kernels that wrote them)
+struct Fold {
+    uint32_t rearm_shards = 0;           // the scan pulled its tiles from this many work counters: the fold zeroes them for the next scan
+    const uint32_t *alt_flag = nullptr;  // speculative routes: if this flag is up the companion kernel redid the launch ...
+    int alt_rows = 0;                    // ... and left this many rows in place of the first kernel's
+    bool undigested = false;             // k > 32 partials: their k-mers are counted in NTK_ACC_UNDIGESTED as well
+};
+int launch_fold(ntk_ctx *c, int rows, const Fold &f = Fold())
+{
+    hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream, (const uint32_t *)c->d_part_hist,
+                       (const uint64_t *)c->d_part_scalars, rows, c->d_acc, f.rearm_shards ? c->d_work : (uint32_t *)nullptr, (int)f.rearm_shards,
+                       f.alt_flag, f.alt_rows, f.undigested ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    if (f.rearm_shards) c->work_dirty = false;
+    return NTK_OK;
+}
+
+inline bool bad_device_input(const uint8_t *d_seq, const uint8_t *d_qual) { return !d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15); }
+
+// The quality switch.  ScanArgs kernels read the stream from their arguments (cutoff 0 masks nothing: the plain build runs) ...
+inline void scan_args_set_quality(ScanArgs &a, const uint8_t *d_qual, uint32_t cutoff)
+{
+    if (!cutoff) return;
+    const QualityCut qc = quality_cut(cutoff);
+    a.qual = d_qual; a.q_add = qc.add; a.q_sel = qc.sel;
+}
+// ... the byte-walking and k > 32 kernels have a quality build that takes (qual, q_add, q_sel) as three trailing arguments (ntk_kernels.hpp
+// QualIn): kernel_q with d_qual set (masking at `cutoff`, 1..255), the plain kernel without.
+template <class KernelQ, class Kernel, class... Args>
+void launch_with_quality(ntk_ctx *c, KernelQ kernel_q, Kernel kernel, int blocks, int threads, const uint8_t *d_qual, uint32_t cutoff, Args... args)
+{
+    if (d_qual) {
+        const QualityCut qc = quality_cut(cutoff);
+        hipLaunchKernelGGL(kernel_q, dim3(blocks), dim3(threads), 0, c->stream, args..., d_qual, qc.add, qc.sel);
+    } else
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, c->stream, args...);
+}
+
+// CanonicalKmers over raw (un-normalised) bytes into the accumulators: canonical_bytes_reduce_kernel + fold (ntk_kernels.hpp).
+inline int raw_bytes_blocks(const ntk_ctx *c, uint64_t n) { return blocks_for(c, n, (uint64_t)kPlThreads * 32, 8); }   // (32 starts per thread)
 
 // the quality builds of the byte-walking and k > 32 kernels: (qual, q_add, q_sel) as three trailing arguments (ntk_kernels.hpp QualIn)
 template <bool WIDE> constexpr auto bytes_reduce_q = &canonical_bytes_reduce_kernel<WIDE, true, const uint8_t *, uint32_t, uint32_t>;
 template <bool ACCEPT_U> constexpr auto wide_reduce_q = &wide_canonical_reduce_kernel<ACCEPT_U, true, const uint8_t *, uint32_t, uint32_t>;
 
-// canonical_bytes_reduce_kernel<WIDE> over d_seq[0, n), or its quality build when d_qual is set (masking at `cutoff`, 1..255).
-template <bool WIDE>
-void launch_raw_bytes(ntk_ctx *c, int blocks, const uint8_t *d_seq, uint64_t n, uint32_t k, const uint32_t *run_if, uint32_t normalized,
+// canonical_bytes_reduce_kernel<wide> over d_seq[0, n), or its quality build when d_qual is set.
+void launch_raw_bytes(ntk_ctx *c, bool wide, int blocks, const uint8_t *d_seq, uint64_t n, uint32_t k, const uint32_t *run_if, bool normalized,
                       const uint8_t *d_qual, uint32_t cutoff)
 {
     const uint32_t pb = k < 6 ? k : 6;
-    if (d_qual) {
-        const QualityCut qc = quality_cut(cutoff);
-        hipLaunchKernelGGL(bytes_reduce_q<WIDE>, dim3(blocks), dim3(kPlThreads), 0, c->stream, d_seq, n, (n + 15) & ~(uint64_t)15, k,
-                           2u * (k - pb), (const uint16_t *)(c->d_lut + 768), c->d_part_hist, c->d_part_scalars, run_if, normalized, d_qual, qc.add, qc.sel);
-    } else {
-        hipLaunchKernelGGL(canonical_bytes_reduce_kernel<WIDE>, dim3(blocks), dim3(kPlThreads), 0, c->stream, d_seq, n, (n + 15) & ~(uint64_t)15, k,
-                           2u * (k - pb), (const uint16_t *)(c->d_lut + 768), c->d_part_hist, c->d_part_scalars, run_if, normalized);
-    }
+    launch_with_quality(c, wide ? bytes_reduce_q<true> : bytes_reduce_q<false>, wide ? &canonical_bytes_reduce_kernel<true> : &canonical_bytes_reduce_kernel<false>,
+                        blocks, kPlThreads, d_qual, cutoff, d_seq, n, (n + 15) & ~(uint64_t)15, k, 2u * (k - pb), (const uint16_t *)(c->d_lut + 768),
+                        c->d_part_hist, c->d_part_scalars, run_if, wide && normalized ? 1u : 0u);
 }
 
-// d_qual (with cutoff 1..255): the quality stream, masked before the walk (NULL: none).
-int run_raw_bytes_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, bool zero_first, bool normalized,
-                         const uint8_t *d_qual, uint32_t cutoff)
+// The reduce routes of the byte path that no packed-value scan serves alone (d_qual with cutoff 1..255: the quality stream, masked before the
+// walk; NULL: none).  k <= 32 on input that was not normalised: canonical_bytes_reduce_kernel<false> walks the raw bytes.
+// k = 33..255 (counters + histogram): wide_canonical_reduce_kernel decides the strand on the first 32 bases of the packed 2-bit streams;
+// canonical_bytes_reduce_kernel<true> is queued behind it and returns at once unless that launch raised its flag (two k-mers equal over 32
+// bases, or - on input that was not normalised - a byte with bit 5 set), and the fold takes whichever partials are valid.  No host round
+// trip; 0.9 ms instead of 9.5 per 1.5 GB at k = 64 (profiles/r06r).  Under NTK_ROUTE_NO_SPECULATION the byte walk runs alone.
+int run_bytes_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, bool zero_first, bool normalized,
+                     const uint8_t *d_qual, uint32_t cutoff)
 {
+    const bool wide = p->k > 32, packed_first = wide && !(c->route_off & NTK_ROUTE_NO_SPECULATION);
     if (zero_first) HIPCHK(hipMemsetAsync(c->d_acc, 0, NTK_ACC_WORDS * sizeof(uint64_t), c->stream));
-    const int blocks = raw_bytes_blocks(c, n);
-    int rc = ensure_partials(c, blocks);
-    if (rc) return rc;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {
-        rc = get_event(c, &e0); if (rc) return rc;
-        rc = get_event(c, &e1); if (rc) { c->ev_free.push_back(e0); return rc; }
-        HIPCHK(hipEventRecord(e0, c->stream));
-    }
-    if (p->k > 32) launch_raw_bytes<true>(c, blocks, d_seq, n, p->k, nullptr, normalized ? 1u : 0u, d_qual, cutoff);
-    else launch_raw_bytes<false>(c, blocks, d_seq, n, p->k, nullptr, 0u, d_qual, cutoff);
-    HIPCHK(hipGetLastError());
-    if (c->timing) { HIPCHK(hipEventRecord(e1, c->stream)); c->ev_used.emplace_back(e0, e1); }
-    hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream,
-                       (const uint32_t *)c->d_part_hist, (const uint64_t *)c->d_part_scalars, blocks, c->d_acc, (uint32_t *)nullptr, 0,
-                       (const uint32_t *)nullptr, 0, p->k > 32 ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    return NTK_OK;
-}
-
-// CanonicalKmers with k = 33..255 (counters + histogram): wide_canonical_reduce_kernel decides the strand on the first 32 bases of the packed
-// 2-bit streams; canonical_bytes_reduce_kernel<true> is queued behind it and returns at once unless that launch raised its flag (two k-mers
-// equal over 32 bases, or - on input that was not normalised - a byte with bit 5 set), and the fold takes whichever partials are valid.  No
-// host round trip; 0.9 ms instead of 9.5 per 1.5 GB at k = 64 (profiles/r06r).  The direct route under NTK_ROUTE_NO_SPECULATION.
-int run_wide_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, bool zero_first, bool normalized,
-                    const uint8_t *d_qual, uint32_t cutoff)
-{
-    if (c->route_off & NTK_ROUTE_NO_SPECULATION) return run_raw_bytes_reduce(c, d_seq, n, p, zero_first, normalized, d_qual, cutoff);
-    if (zero_first) HIPCHK(hipMemsetAsync(c->d_acc, 0, NTK_ACC_WORDS * sizeof(uint64_t), c->stream));
-    const uint64_t n_tiles = (n + kWkTile - 1) / kWkTile;
-    const uint64_t max_blocks = c->launch_blocks > 0 ? (uint64_t)c->launch_blocks : (uint64_t)c->n_cu * 8;
-    const int blocks = (int)(n_tiles < max_blocks ? n_tiles : max_blocks), blocks_raw = raw_bytes_blocks(c, n);
+    const int blocks_raw = raw_bytes_blocks(c, n), blocks = packed_first ? blocks_for(c, n, kWkTile, 8) : blocks_raw;
     int rc = ensure_partials(c, blocks > blocks_raw ? blocks : blocks_raw);
     if (rc) return rc;
-    uint32_t *flag = c->d_lower + c->lower_idx;
-    c->lower_idx = (c->lower_idx + 1) % kLowerRing;
-    uint32_t *flag_next = c->d_lower + c->lower_idx;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {
-        rc = get_event(c, &e0); if (rc) return rc;
-        rc = get_event(c, &e1); if (rc) { c->ev_free.push_back(e0); return rc; }
-        HIPCHK(hipEventRecord(e0, c->stream));
+    Fold fold;
+    fold.undigested = wide;
+    TimedSpan span;
+    if ((rc = span.begin(c))) return rc;
+    if (packed_first) {
+        const FlagPair f = next_flag(c);
+        launch_with_quality(c, normalized ? wide_reduce_q<true> : wide_reduce_q<false>,
+                            normalized ? &wide_canonical_reduce_kernel<true> : &wide_canonical_reduce_kernel<false>, blocks, kWkThreads, d_qual, cutoff,
+                            d_seq, n, p->k, c->d_part_hist, c->d_part_scalars, f.flag, f.next);
+        HIPCHK(hipGetLastError());
+        fold.alt_flag = f.flag; fold.alt_rows = blocks_raw;
     }
-    if (d_qual) {
-        const QualityCut qc = quality_cut(cutoff);
-        if (normalized)
-            hipLaunchKernelGGL(wide_reduce_q<true>, dim3(blocks), dim3(kWkThreads), 0, c->stream, d_seq, n, p->k, c->d_part_hist, c->d_part_scalars,
-                               flag, flag_next, d_qual, qc.add, qc.sel);
-        else
-            hipLaunchKernelGGL(wide_reduce_q<false>, dim3(blocks), dim3(kWkThreads), 0, c->stream, d_seq, n, p->k, c->d_part_hist, c->d_part_scalars,
-                               flag, flag_next, d_qual, qc.add, qc.sel);
-    } else if (normalized)
-        hipLaunchKernelGGL(wide_canonical_reduce_kernel<true>, dim3(blocks), dim3(kWkThreads), 0, c->stream, d_seq, n, p->k, c->d_part_hist, c->d_part_scalars, flag, flag_next);
-    else
-        hipLaunchKernelGGL(wide_canonical_reduce_kernel<false>, dim3(blocks), dim3(kWkThreads), 0, c->stream, d_seq, n, p->k, c->d_part_hist, c->d_part_scalars, flag, flag_next);
+    launch_raw_bytes(c, wide, blocks_raw, d_seq, n, p->k, fold.alt_flag, normalized, d_qual, cutoff);
     HIPCHK(hipGetLastError());
-    launch_raw_bytes<true>(c, blocks_raw, d_seq, n, p->k, (const uint32_t *)flag, normalized ? 1u : 0u, d_qual, cutoff);
-    HIPCHK(hipGetLastError());
-    if (c->timing) { HIPCHK(hipEventRecord(e1, c->stream)); c->ev_used.emplace_back(e0, e1); }
-    hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream,
-                       (const uint32_t *)c->d_part_hist, (const uint64_t *)c->d_part_scalars, blocks, c->d_acc, (uint32_t *)nullptr, 0,
-                       (const uint32_t *)flag, blocks_raw, 1);
-    HIPCHK(hipGetLastError());
+    if ((rc = span.end(c->ev_used))) return rc;
+    return launch_fold(c, blocks, fold);
+}
+
+// One scan of a pull-model kernel that takes a ScanArgs (scan_kernel, scan2_kernel, minimizer_scan_kernel) over a.seq[0, a.n_bytes).
+// The caller picks the build and its geometry (TileScan) and fills what is its own in `a`: k, window, quality stream, output planes.
+// Everything else is done here, once: the launch ranges of at most kMaxTilesPerLaunch tiles, shards and tiles per pull, the work counters,
+// zero_acc on the first launch only, the partials, the timed span and - in reduce mode - the fold.
+struct TileScan {
+    const void *fn = nullptr;
+    int threads = 0;
+    size_t lds = 0;           // dynamic LDS per block
+    uint32_t halo_lanes = 0;  // a tile emits 64 - halo_lanes slots of 16 positions
+    uint64_t max_chunk = 0;   // cap on tiles per pull
+    int max_per_cu = 0;       // cap on resident blocks per CU; the auto grid is exactly the resident blocks (work is pulled: more only write empty histograms, +1.5 %)
+    bool reduce = true;       // partials + fold; a materialise scan has neither
+    bool speculate = false;   // the SPEC build on un-normalised byte-path input: canonical_bytes_reduce_kernel<false> is queued behind the scan,
+    uint32_t cutoff = 0;      // ... masking a.qual at this cutoff (0: no quality stream)
+};
+inline uint64_t tile_count(uint64_t n, uint64_t tile_slots) { return ((n + 15) / 16 + tile_slots - 1) / tile_slots; }
+int launch_tile_scan(ntk_ctx *c, const TileScan &s, ScanArgs &a, bool zero_first)   // zero_first: the first launch zeroes the accumulators in its prologue
+{
+    int per_cu = 0, rc = resident_blocks(c, s.fn, s.threads, s.lds, s.max_per_cu, &per_cu);
+    if (rc) return rc;
+    const uint64_t blocks_max = block_cap(c, per_cu), waves_per_block = (uint64_t)s.threads / 64;
+    const uint64_t tile_slots = 64 - (uint64_t)s.halo_lanes, tile_stride = tile_slots * 16, n = a.n_bytes;
+    const int blocks_raw = s.speculate ? raw_bytes_blocks(c, n) : 0;
+    a.n_tiles = tile_count(n, tile_slots);
+    a.work_counters = c->d_work;
+    a.zero_words = NTK_ACC_WORDS;
+    for (uint64_t tb = 0; tb < a.n_tiles; tb += kMaxTilesPerLaunch) {
+        const uint64_t te = tb + kMaxTilesPerLaunch < a.n_tiles ? tb + kMaxTilesPerLaunch : a.n_tiles;
+        const uint64_t tiles = te - tb;
+        uint64_t chunk = tiles / (blocks_max * waves_per_block * 4);  // >= ~4 pulls per wave, <= max_chunk tiles each (8..32 are within 1 %: profiles/r02c)
+        chunk = chunk < 1 ? 1 : (chunk > s.max_chunk ? s.max_chunk : chunk);
+        const uint64_t want_blocks = (tiles + chunk * waves_per_block - 1) / (chunk * waves_per_block);
+        const int blocks = (int)(want_blocks < blocks_max ? want_blocks : blocks_max);
+        a.tile_begin = tb; a.tile_end = te;
+        const uint64_t first_tail = n / tile_stride;   // tiles t with (t + 1) * tile_stride > n_bytes touch the end of the input
+        a.tail_tile_rel = first_tail < tb ? 0u : (first_tail - tb > 0xFFFFFFFEull ? 0xFFFFFFFFu : (uint32_t)(first_tail - tb));
+        a.n_shards = blocks < kMaxShards ? (uint32_t)blocks : (uint32_t)kMaxShards;
+        a.tiles_per_shard = (uint32_t)((tiles + a.n_shards - 1) / a.n_shards);
+        a.chunk_tiles = (uint32_t)chunk;
+        a.zero_acc = zero_first ? c->d_acc : nullptr;
+        zero_first = false;
+        // the work counters are zero on entry: the fold of the previous reduce scan re-armed them (launch_fold); anything else
+        // (first use, a materialise scan, an error on the way) leaves work_dirty set and costs a memset here
+        if (c->work_dirty) HIPCHK(hipMemsetAsync(c->d_work, 0, kMaxShards * 64, c->stream));
+        c->work_dirty = true;
+        if (s.reduce) {
+            if ((rc = ensure_partials(c, blocks > blocks_raw ? blocks : blocks_raw))) return rc;
+            a.part_hist = c->d_part_hist; a.part_scalars = c->d_part_scalars;
+        }
+        Fold fold;
+        fold.rearm_shards = a.n_shards;
+        if (s.speculate) {
+            const FlagPair f = next_flag(c);
+            a.lower_flag = f.flag; a.lower_flag_next = f.next;
+            fold.alt_flag = f.flag; fold.alt_rows = blocks_raw;
+        }
+        TimedSpan span;
+        if ((rc = span.begin(c))) return rc;
+        void *kargs[] = {(void *)&a};
+        HIPCHK(hipLaunchKernel(s.fn, dim3(blocks), dim3(s.threads), kargs, s.lds, c->stream));
+        if (s.speculate) {   // (inside the timed span: the pair is this route's scan)
+            launch_raw_bytes(c, false, blocks_raw, a.seq, n, a.k, fold.alt_flag, false, a.qual, s.cutoff);
+            HIPCHK(hipGetLastError());
+        }
+        if ((rc = span.end(c->ev_used))) return rc;
+        if (s.reduce && (rc = launch_fold(c, blocks, fold))) return rc;
+    }
     return NTK_OK;
 }
 
-// One scan over d_seq[0, n): launches cover at most kMaxTilesPerLaunch tiles each so that per-block u32
-// histogram cells and 32-bit buffer offsets cannot overflow.
+// The k-mer scans (reduce and materialise) and the register-fused minimizer builds of scan2_kernel.
 int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, const Mode &m, bool reduce,
              uint64_t *d_values, uint16_t *d_valid16, uint16_t *d_rc16, const uint8_t *d_qual = nullptr, const void *fused_min_fn = nullptr,
              int halo_lanes = kHaloLanes)   // 3 for the fused-minimizer builds whose windows need more than 32 bytes (ntk_tile.hpp Sv2Geom)
 {
-    const uint64_t tile_slots = 64 - (uint64_t)halo_lanes, tile_stride = tile_slots * 16;
-    bool zero_first = reduce && (p->flags & NTK_FLAG_RESET);   // the first launch zeroes the accumulators in its prologue
+    const bool zero_first = reduce && (p->flags & NTK_FLAG_RESET);
     if (n == 0) {
         if (zero_first) HIPCHK(hipMemsetAsync(c->d_acc, 0, NTK_ACC_WORDS * sizeof(uint64_t), c->stream));
         return NTK_OK;
     }
-    if (!d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15)) return NTK_ERR_BAD_ARG;
+    if (bad_device_input(d_seq, d_qual)) return NTK_ERR_BAD_ARG;
     const uint32_t cutoff = d_qual ? quality_cutoff(p) : 0u;  // cutoff 0 masks nothing: the plain build runs
-    const uint64_t kMaxTilesPerLaunch = (uint64_t)8 << 22;
     bool speculate = false;
     if (m.raw_bytes) {
         // byte path on input that was not normalised: reduce mode only; dense values and windowed minimizers on such input are not built
@@ -395,15 +516,10 @@ int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, 
         // bit 5), the raw-byte kernel is queued behind it and returns at once unless the flag went up, and the fold takes whichever partials
         // are valid: no host round trip, 0.45 ms instead of 5.1 per 1.5 GB of upper-case reads.  One launch only (the raw-byte kernel works on
         // window starts, the scan on window ends: their launch ranges do not line up), the direct route otherwise and under NTK_ROUTE_NO_SPECULATION.
-        const uint64_t tiles_all = ((n + 15) / 16 + tile_slots - 1) / tile_slots;
-        speculate = p->k <= 32 && tiles_all <= kMaxTilesPerLaunch && !(c->route_off & NTK_ROUTE_NO_SPECULATION);
-        if (p->k > 32) return run_wide_reduce(c, d_seq, n, p, zero_first, m.accept_u, qual, cutoff);
-        if (!speculate) return run_raw_bytes_reduce(c, d_seq, n, p, zero_first, false, qual, cutoff);
+        speculate = p->k <= 32 && tile_count(n, 64 - (uint64_t)halo_lanes) <= kMaxTilesPerLaunch && !(c->route_off & NTK_ROUTE_NO_SPECULATION);
+        if (!speculate) return run_bytes_reduce(c, d_seq, n, p, zero_first, m.accept_u, qual, cutoff);   // (accept_u: only k > 32 comes here normalised)
     }
-    // materialise mode stages 8.7 KiB per wave through LDS: 256-thread blocks, 4 per CU
-    const void *fn = fused_min_fn ? fused_min_fn
-                   : cutoff ? (reduce ? pick_scan<true, true>(m, p->k) : pick_scan<false, true>(m, p->k))
-                            : (reduce ? pick_scan<true, false>(m, p->k) : pick_scan<false, false>(m, p->k));   // (speculate: tie_rc, !accept_u - the SPEC build)
+    const void *fn = fused_min_fn ? fused_min_fn : pick_scan(m, p->k, reduce, cutoff != 0);   // (speculate: tie_rc, !accept_u - the SPEC build)
     if (!fn) return NTK_ERR_BAD_ARG;
     // every reduce-mode scan (any path, any k, with or without a quality stream, fused minimizers) is a scan2 build: 768 threads, two
     // blocks per CU = 6 waves per SIMD, which needs <= 80 VGPRs.  A build above that would get ONE 768-thread block per CU; it runs
@@ -424,91 +540,20 @@ int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, 
             c->auto_threads[fn] = threads;
         }
     }
-    const int waves_per_block = threads / 64;
-    const size_t lds = reduce ? 0 : (size_t)waves_per_block * kStageWaveU64 * sizeof(uint64_t);  // materialise staging
-    // auto grid: exactly the blocks that are resident at once (work is pulled, so a second round of blocks would only
-    // zero and write out empty histograms: measured +1.5 % at config 2).  Reduce builds: two blocks of `threads` (768, or 640 / 512
-    // for a build above 80 VGPRs: chosen above) per CU, each with its 64 KiB LDS histogram; materialise: 4 x 256 (LDS staging).
-    int per_cu = 0;
-    auto it = c->occupancy.find(std::make_pair(fn, threads));
-    if (it != c->occupancy.end()) per_cu = it->second;
-    else {
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds));
-        if (per_cu < 1) per_cu = 1;
-        const int cap = reduce ? 2 * (1024 / threads) : 4;
-        if (per_cu > cap) per_cu = cap;
-        c->occupancy[std::make_pair(fn, threads)] = per_cu;
-    }
-    const int blocks_max = c->launch_blocks > 0 ? c->launch_blocks : c->n_cu * per_cu;
+    // Reduce builds: two blocks of `threads` (768, or 640 / 512 for a build above 80 VGPRs: chosen above) per CU, each with its 64 KiB LDS
+    // histogram, <= 24 tiles per pull; materialise stages 8.7 KiB per wave through LDS: 256-thread blocks, 4 per CU.
+    TileScan s;
+    s.fn = fn; s.threads = threads; s.halo_lanes = (uint32_t)halo_lanes; s.max_chunk = 24;
+    s.lds = reduce ? 0 : (size_t)(threads / 64) * kStageWaveU64 * sizeof(uint64_t);
+    s.max_per_cu = reduce ? 2 * (1024 / threads) : 4;
+    s.reduce = reduce; s.speculate = speculate; s.cutoff = cutoff;
     ScanArgs a;
     memset(&a, 0, sizeof(a));
     scan_args_set_k(a, p->k);
-    a.seq = d_seq;
-    a.n_bytes = n;
-    a.n_tiles = ((n + 15) / 16 + tile_slots - 1) / tile_slots;
+    a.seq = d_seq; a.n_bytes = n;
     a.values = d_values; a.valid16 = d_valid16; a.rc16 = d_rc16;
-    if (cutoff) { const QualityCut qc = quality_cut(cutoff); a.qual = d_qual; a.q_add = qc.add; a.q_sel = qc.sel; }
-    // per launch: a shard holds <= 2^22 tiles so that the per-block u32 histogram cells (a block can at most drain its
-    // whole shard: 2^22 * 992 windows) and the u32 work counters cannot overflow
-    for (uint64_t tb = 0; tb < a.n_tiles; tb += kMaxTilesPerLaunch) {
-        const uint64_t te = tb + kMaxTilesPerLaunch < a.n_tiles ? tb + kMaxTilesPerLaunch : a.n_tiles;
-        const uint64_t tiles = te - tb;
-        uint64_t chunk = tiles / ((uint64_t)blocks_max * waves_per_block * 4);  // >= ~4 pulls per wave, <= 24 tiles each (8..32 are within 1 %: profiles/r02c)
-        chunk = chunk < 1 ? 1 : (chunk > 24 ? 24 : chunk);
-        const uint64_t want_blocks = (tiles + chunk * waves_per_block - 1) / (chunk * waves_per_block);
-        const int blocks = (int)(want_blocks < (uint64_t)blocks_max ? want_blocks : (uint64_t)blocks_max);
-        a.tile_begin = tb; a.tile_end = te;
-        {   // tiles t with (t + 1) * 992 > n_bytes touch the end of the input: t >= n_bytes / 992
-            const uint64_t first_tail = n / tile_stride;
-            a.tail_tile_rel = first_tail < tb ? 0u : (first_tail - tb > 0xFFFFFFFEull ? 0xFFFFFFFFu : (uint32_t)(first_tail - tb));
-        }
-        a.n_shards = blocks < kMaxShards ? (uint32_t)blocks : (uint32_t)kMaxShards;
-        a.tiles_per_shard = (uint32_t)((tiles + a.n_shards - 1) / a.n_shards);
-        a.chunk_tiles = (uint32_t)chunk;
-        a.work_counters = c->d_work;
-        a.zero_acc = zero_first ? c->d_acc : nullptr; a.zero_words = NTK_ACC_WORDS;
-        zero_first = false;
-        // the work counters are zero on entry: the fold kernel of the previous reduce scan re-armed them; anything else
-        // (first use, a materialise scan, an error on the way) leaves work_dirty set and costs a memset here
-        if (c->work_dirty) HIPCHK(hipMemsetAsync(c->d_work, 0, kMaxShards * 64, c->stream));
-        c->work_dirty = true;
-        const int blocks_raw = speculate ? raw_bytes_blocks(c, n) : 0;
-        if (reduce) {
-            int rc = ensure_partials(c, blocks > blocks_raw ? blocks : blocks_raw);
-            if (rc) return rc;
-            a.part_hist = c->d_part_hist; a.part_scalars = c->d_part_scalars;
-        }
-        uint32_t *flag = nullptr;
-        if (speculate) {
-            flag = c->d_lower + c->lower_idx;
-            c->lower_idx = (c->lower_idx + 1) % kLowerRing;
-            a.lower_flag = flag; a.lower_flag_next = c->d_lower + c->lower_idx;
-        }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (c->timing) {
-            int rc = get_event(c, &e0); if (rc) return rc;
-            rc = get_event(c, &e1); if (rc) { c->ev_free.push_back(e0); return rc; }
-            HIPCHK(hipEventRecord(e0, c->stream));
-        }
-        void *kargs[] = {(void *)&a};
-        HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(threads), kargs, lds, c->stream));
-        if (speculate) {   // (inside the timed span: the pair is this route's scan)
-            launch_raw_bytes<false>(c, blocks_raw, d_seq, n, p->k, (const uint32_t *)flag, 0u, cutoff ? d_qual : nullptr, cutoff);
-            HIPCHK(hipGetLastError());
-        }
-        if (c->timing) {
-            HIPCHK(hipEventRecord(e1, c->stream));
-            c->ev_used.emplace_back(e0, e1);
-        }
-        if (reduce) {
-            hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream,
-                               (const uint32_t *)c->d_part_hist, (const uint64_t *)c->d_part_scalars, blocks, c->d_acc, c->d_work, (int)a.n_shards,
-                               (const uint32_t *)flag, blocks_raw, 0);
-            HIPCHK(hipGetLastError());
-            c->work_dirty = false;
-        }
-    }
-    return NTK_OK;
+    scan_args_set_quality(a, d_qual, cutoff);
+    return launch_tile_scan(c, s, a, zero_first);
 }
 
 // Generic fused windowed minimizers (ntk_kernels.hpp minimizer_scan_kernel): any k <= 31 and w <= 49 of the canonical paths, with or
@@ -532,69 +577,21 @@ const void *pick_min_generic(const Mode &m, bool quality, bool f64, uint32_t k) 
 
 int run_min_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, const Mode &m, uint32_t w, const uint8_t *d_qual)
 {
-    if (!d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15)) return NTK_ERR_BAD_ARG;
+    if (bad_device_input(d_seq, d_qual)) return NTK_ERR_BAD_ARG;
     const uint32_t cutoff = d_qual ? quality_cutoff(p) : 0u;
     const bool f64 = p->k <= 25 && !(c->route_off & NTK_ROUTE_NO_F64);
-    const void *fn = pick_min_generic(m, cutoff != 0, f64, p->k);
-    if (!fn) return NTK_ERR_BAD_ARG;
-    const int threads = min_gen_threads(f64);   // 512: two blocks per CU, 768: one (ntk_kernels.hpp), each with its 64 KiB LDS histogram
-    int per_cu = 0;
-    auto it = c->occupancy.find(std::make_pair(fn, threads));
-    if (it != c->occupancy.end()) per_cu = it->second;
-    else {
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0));
-        if (per_cu < 1) per_cu = 1;
-        if (per_cu > 8) per_cu = 8;
-        c->occupancy[std::make_pair(fn, threads)] = per_cu;
-    }
-    const int blocks_max = c->launch_blocks > 0 ? c->launch_blocks : c->n_cu * per_cu;
-    const int waves_per_block = threads / 64;
     ScanArgs a;
     memset(&a, 0, sizeof(a));
     scan_args_set_k(a, p->k);
     a.seq = d_seq; a.n_bytes = n;
-    if (cutoff) { const QualityCut qc = quality_cut(cutoff); a.qual = d_qual; a.q_add = qc.add; a.q_sel = qc.sel; }
+    scan_args_set_quality(a, d_qual, cutoff);
     scan_args_set_window(a, w);   // halo lanes, the validity smear, the overlap of the two power-of-two windows (ntk_tile.hpp)
-    const uint64_t slots = 64 - a.min_halo_lanes, stride = slots * 16;
-    a.n_tiles = ((n + 15) / 16 + slots - 1) / slots;
-    bool zero_first = (p->flags & NTK_FLAG_RESET) != 0;
-    const uint64_t kMaxTilesPerLaunch = (uint64_t)8 << 22;
-    for (uint64_t tb = 0; tb < a.n_tiles; tb += kMaxTilesPerLaunch) {
-        const uint64_t te = tb + kMaxTilesPerLaunch < a.n_tiles ? tb + kMaxTilesPerLaunch : a.n_tiles;
-        const uint64_t tiles = te - tb;
-        uint64_t chunk = tiles / ((uint64_t)blocks_max * waves_per_block * 4);
-        chunk = chunk < 1 ? 1 : (chunk > 16 ? 16 : chunk);
-        const uint64_t want_blocks = (tiles + chunk * waves_per_block - 1) / (chunk * waves_per_block);
-        const int blocks = (int)(want_blocks < (uint64_t)blocks_max ? want_blocks : (uint64_t)blocks_max);
-        a.tile_begin = tb; a.tile_end = te;
-        const uint64_t first_tail = n / stride;
-        a.tail_tile_rel = first_tail < tb ? 0u : (first_tail - tb > 0xFFFFFFFEull ? 0xFFFFFFFFu : (uint32_t)(first_tail - tb));
-        a.n_shards = blocks < kMaxShards ? (uint32_t)blocks : (uint32_t)kMaxShards;
-        a.tiles_per_shard = (uint32_t)((tiles + a.n_shards - 1) / a.n_shards);
-        a.chunk_tiles = (uint32_t)chunk;
-        a.work_counters = c->d_work;
-        a.zero_acc = zero_first ? c->d_acc : nullptr; a.zero_words = NTK_ACC_WORDS;
-        zero_first = false;
-        if (c->work_dirty) HIPCHK(hipMemsetAsync(c->d_work, 0, kMaxShards * 64, c->stream));
-        c->work_dirty = true;
-        int rc = ensure_partials(c, blocks);
-        if (rc) return rc;
-        a.part_hist = c->d_part_hist; a.part_scalars = c->d_part_scalars;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (c->timing) {
-            rc = get_event(c, &e0); if (rc) return rc;
-            rc = get_event(c, &e1); if (rc) { c->ev_free.push_back(e0); return rc; }
-            HIPCHK(hipEventRecord(e0, c->stream));
-        }
-        void *kargs[] = {(void *)&a};
-        HIPCHK(hipLaunchKernel(fn, dim3(blocks), dim3(threads), kargs, 0, c->stream));
-        if (c->timing) { HIPCHK(hipEventRecord(e1, c->stream)); c->ev_used.emplace_back(e0, e1); }
-        hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream,
-                           (const uint32_t *)c->d_part_hist, (const uint64_t *)c->d_part_scalars, blocks, c->d_acc, c->d_work, (int)a.n_shards);
-        HIPCHK(hipGetLastError());
-        c->work_dirty = false;
-    }
-    return NTK_OK;
+    TileScan s;
+    s.fn = pick_min_generic(m, cutoff != 0, f64, p->k);
+    if (!s.fn) return NTK_ERR_BAD_ARG;
+    s.threads = min_gen_threads(f64);   // 512: two blocks per CU, 768: one (ntk_kernels.hpp), each with its 64 KiB LDS histogram
+    s.halo_lanes = a.min_halo_lanes; s.max_chunk = 16; s.max_per_cu = 8;
+    return launch_tile_scan(c, s, a, (p->flags & NTK_FLAG_RESET) != 0);
 }
 
 void destroy_batch(ntk_batch *b)
@@ -1767,9 +1764,7 @@ static int minimizers_reduce_impl(ntk_ctx *c, const uint8_t *d_seq, const uint8_
                                c->d_part_scalars, c0 - start);
         }
 #undef NTK_WM
-        hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream,
-                           (const uint32_t *)c->d_part_hist, (const uint64_t *)c->d_part_scalars, blocks, c->d_acc);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch_fold(c, blocks))) return rc;   // (no work counters to re-arm: the materialise scan left them dirty)
     }
     return NTK_OK;
 }
@@ -2029,36 +2024,29 @@ int ntk_allreduce_accumulators(ntk_comm *m)
     if (!m) return NTK_ERR_BAD_ARG;
     const RcclApi &R = load_rccl();
     if (!R.ok) { g_last_rccl = -1; return NTK_ERR_RCCL; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    TimedSpan span;   // the collective's own duration on this rank (ntk_comm_allreduce_time_ms): events on the stream it runs on; a failure
+                      // below loses the timing of this call, not the events
     ntk_ctx *c0 = m->ctxs.empty() ? nullptr : m->ctxs[0];
-    if (c0 && c0->timing) {   // the collective's own duration on this rank (ntk_comm_allreduce_time_ms): events on the stream it runs on
+    if (c0 && c0->timing) {
         HIPCHK(hipSetDevice(c0->device));
-        int rc = get_event(c0, &e0); if (rc) return rc;
-        rc = get_event(c0, &e1); if (rc) { c0->ev_free.push_back(e0); return rc; }
-        HIPCHK(hipEventRecord(e0, c0->stream));
+        int rc = span.begin(c0);
+        if (rc) return rc;
     }
-    // from here on a failure hands the event pair back to the ctx's pool (the timing of this call is lost, the events are not)
-    auto fail = [&](int status) { if (e0) { c0->ev_free.push_back(e0); c0->ev_free.push_back(e1); } return status; };
     ncclResult_t r = R.GroupStart();
-    if (r != ncclSuccess) { g_last_rccl = (int)r; return fail(NTK_ERR_RCCL); }
+    if (r != ncclSuccess) { g_last_rccl = (int)r; return NTK_ERR_RCCL; }
     for (size_t i = 0; i < m->ctxs.size(); i++) {
         ntk_ctx *c = m->ctxs[i];
         r = R.AllReduce(c->d_acc, c->d_acc, NTK_ACC_WORDS, ncclUint64, ncclSum, m->comms[i], c->stream);
-        if (r != ncclSuccess) { (void)R.GroupEnd(); g_last_rccl = (int)r; return fail(NTK_ERR_RCCL); }
+        if (r != ncclSuccess) { (void)R.GroupEnd(); g_last_rccl = (int)r; return NTK_ERR_RCCL; }
     }
-    if ((r = R.GroupEnd()) != ncclSuccess) { g_last_rccl = (int)r; return fail(NTK_ERR_RCCL); }
+    if ((r = R.GroupEnd()) != ncclSuccess) { g_last_rccl = (int)r; return NTK_ERR_RCCL; }
     for (ntk_ctx *c : m->ctxs) {
-        hipError_t e = hipSetDevice(c->device);
-        if (e == hipSuccess) { hipLaunchKernelGGL(xor_from_bit_counters_kernel, dim3(1), dim3(64), 0, c->stream, c->d_acc); e = hipGetLastError(); }
-        if (e != hipSuccess) { g_last_hip = (int)e; return fail(NTK_ERR_HIP); }
+        HIPCHK(hipSetDevice(c->device));
+        hipLaunchKernelGGL(xor_from_bit_counters_kernel, dim3(1), dim3(64), 0, c->stream, c->d_acc);
+        HIPCHK(hipGetLastError());
     }
-    if (e0) {
-        hipError_t e = hipSetDevice(c0->device);
-        if (e == hipSuccess) e = hipEventRecord(e1, c0->stream);
-        if (e != hipSuccess) { g_last_hip = (int)e; (void)hipGetLastError(); return fail(NTK_ERR_HIP); }
-        m->ev_used.emplace_back(e0, e1);
-    }
-    return NTK_OK;
+    if (span.e0) HIPCHK(hipSetDevice(c0->device));
+    return span.end(m->ev_used);
 }
 
 /* Sum of the durations of the all-reduces (collective + xor rebuild, on the first local ctx's stream) issued while that ctx had

@@ -752,7 +752,7 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
     // QM: the watch reads the bytes after quality_break and skips masked ones (lower_watch_or: a lower-case base under a low quality is an N).
     constexpr bool SPEC = TIE_RC && !ACCEPT_U && W == 0 && !FWD;
     uint32_t lc = 0;
-    if (SPEC && a.lower_flag_next && blockIdx.x == 0 && threadIdx.x == 0) *a.lower_flag_next = 0;   // the next launch's flag (a ring, see run_scan)
+    if (SPEC && a.lower_flag_next && blockIdx.x == 0 && threadIdx.x == 0) *a.lower_flag_next = 0;   // the next launch's flag (a ring, see next_flag in ntk_api.hip)
     DevXL xl;
     DevMasks2<K, HB> mp;
     NoSink sink;
@@ -1601,7 +1601,7 @@ __global__ __launch_bounds__(kPlThreads) void canonical_bytes_reduce_kernel(cons
 //     gives it (src/kmer.rs:124-128: ties report the reverse complement).  k >= 33, so 32 bases are a proper prefix; two k-mers that
 //     agree on them (4^-32 per position on random text, but every window of a long inverted repeat) raise *redo_flag, and so does a byte
 //     with bit 5 set when the input was not normalised (lower case: the raw-byte order is then not the 2-bit order) - the host has queued
-//     canonical_bytes_reduce_kernel<true> behind this launch, which then redoes it (run_wide_reduce in ntk_api.hip; the fold takes
+//     canonical_bytes_reduce_kernel<true> behind this launch, which then redoes it (run_bytes_reduce in ntk_api.hip; the fold takes
 //     whichever partials are valid).  ACCEPT_U: the batch is read as Sequence::normalize leaves it (U / u are T, src/sequence.rs:24-51).
 // ---------------------------------------------------------------------------------------------
 // max of x and the value a DPP pattern brings from another lane (lanes the pattern does not reach keep x; every x here is >= -1)

@@ -1,7 +1,7 @@
 """The build manifest: which template instantiation of the scan kernels every reachable call launches.
 
-A plain-Python restatement of the dispatch rules of csrc/ntk_api.hip (resolve_mode, pick_scan, pick_scan_min, pick_min_generic,
-run_scan's raw-byte / speculation branch, run_wide_reduce, minimizers_reduce_impl and its two-pass window_min_reduce_kernel<W> switch) and of
+A plain-Python restatement of the dispatch rules of csrc/ntk_api.hip (resolve_mode, pick_scan / pick_materialise, pick_scan_min, pick_min_generic,
+run_scan's raw-byte / speculation branch, run_bytes_reduce, minimizers_reduce_impl and its two-pass window_min_reduce_kernel<W> switch) and of
 the pick tables of csrc/ntk_scan2.hip.  `calls()` enumerates every reachable call; `kernels(call)` names the matrix kernels it launches, in
 the demangled form `short_name` gives a symbol of the library (`scan2_kernel<21, true, true, false, 14, 0, false>`).  fold_kernel, which
 every reduce call launches as well, is not a matrix kernel (tests/test_build_manifest.py OTHER_KERNELS).
@@ -115,11 +115,11 @@ def kernels(c: Call):
         return None
     if c.entry == "reduce":
         if m.raw_bytes:
-            if c.k > 32:   # run_wide_reduce
+            if c.k > 32:   # run_bytes_reduce, the packed-stream kernel first
                 if c.route & ROUTE_NO_SPECULATION:
                     return (bytes_reduce(True, c.quality),)
                 return (wide_reduce(m.accept_u, c.quality), bytes_reduce(True, c.quality))
-            if c.route & ROUTE_NO_SPECULATION:   # run_raw_bytes_reduce
+            if c.route & ROUTE_NO_SPECULATION:   # run_bytes_reduce, the byte walk alone
                 return (bytes_reduce(False, c.quality),)
             return (scan2(c.k, True, False, c.quality), bytes_reduce(False, c.quality))   # the speculative build, the raw kernel behind it
         return (pick_scan_reduce(m, c.k, c.quality),)

@@ -63,6 +63,28 @@ def _device_u64(n: int, device: int):
     return torch.empty(max(n, 1), dtype=torch.int64, device=f"cuda:{device}")
 
 
+def upload_records(ctx: Context, records, pre: int):
+    """Pack the records with the batch packer (ntk_batch_append: the pre-step's deleted bytes out, one break byte after each) and upload
+    them: (device tensor in the batch layout, n_bytes), or None for no records."""
+    import torch
+    records = list(records)
+    if not records:
+        return None
+    b = Batch(ctx, sum(len(r) for r in records) + len(records), len(records))
+    try:
+        for r in records:
+            if not b.append(bytes(r), pre):
+                raise RuntimeError("batch sized for the records is full")
+        seq, _ = b.buffers()
+        n = int(seq.size)
+        dev = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        dev[:n] = torch.from_numpy(np.array(seq, copy=True)).to(dev.device)
+        torch.cuda.synchronize(dev.device)
+    finally:
+        b.release()
+    return dev, n
+
+
 class CountTable:
     """What the count tables share: a table in device memory behind one library's eight calls.  A subclass names the library
     (_lib_path, _prefix), the u64 words of a key (_key_words) and turns lookup's argument into queries (_queries)."""
@@ -111,26 +133,11 @@ class CountTable:
         self._check("count_device", self._h, C.c_void_p(_ptr(d_seq)), q, n_bytes, C.byref(p))
 
     def count_records(self, records, pre: int):
-        """Pack the records with the batch packer (ntk_batch_append: the pre-step's deleted bytes out, one break byte after each),
-        upload and count them.  Returns when the table has counted them."""
-        import torch
-        records = list(records)
-        if not records:
-            return
-        b = Batch(self.ctx, sum(len(r) for r in records) + len(records), len(records))
-        try:
-            for r in records:
-                if not b.append(bytes(r), pre):
-                    raise RuntimeError("batch sized for the records is full")
-            seq, _ = b.buffers()
-            n = int(seq.size)
-            dev = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
-            dev[:n] = torch.from_numpy(np.array(seq, copy=True)).to(dev.device)
-            torch.cuda.synchronize(dev.device)
-            self.count_device(dev, n, pre)
+        """Pack the records with the batch packer (upload_records), upload and count them.  Returns when the table has counted them."""
+        up = upload_records(self.ctx, records, pre)
+        if up is not None:
+            self.count_device(up[0], up[1], pre)
             self.ctx.synchronize()
-        finally:
-            b.release()
 
     # -- reading -----------------------------------------------------------------------------------------------------------
     def stats(self) -> dict:

@@ -121,40 +121,8 @@ __global__ __launch_bounds__(kThreads) void kt_lookup_kernel(const uint64_t *key
 
 struct ntk_kmer_table : TableCore {
     uint64_t *d_keys = nullptr;
-    // materialise scratch of one chunk (grown on demand)
-    uint64_t scratch_bytes = 0;
-    uint64_t *d_values = nullptr;
-    uint16_t *d_valid16 = nullptr, *d_rc16 = nullptr;
+    MaterialiseScratch scratch;   // of one chunk (grown on demand)
 };
-
-namespace {
-
-void free_scratch(ntk_kmer_table *t)
-{
-    if (t->d_values) (void)hipFree(t->d_values);
-    if (t->d_valid16) (void)hipFree(t->d_valid16);
-    if (t->d_rc16) (void)hipFree(t->d_rc16);
-    t->d_values = nullptr; t->d_valid16 = t->d_rc16 = nullptr; t->scratch_bytes = 0;
-}
-
-int ensure_scratch(ntk_kmer_table *t, uint64_t len)
-{
-    const uint64_t need = (len + 15) & ~(uint64_t)15;
-    if (need <= t->scratch_bytes) return NTK_OK;
-    CT_HIPCHK(hipStreamSynchronize(t->stream));   // the old scratch may still be read by queued kernels
-    free_scratch(t);
-    hipError_t e;
-    if ((e = hipMalloc((void **)&t->d_values, need * sizeof(uint64_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&t->d_valid16, need / 16 * sizeof(uint16_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&t->d_rc16, need / 16 * sizeof(uint16_t))) != hipSuccess) {
-        free_scratch(t);
-        return alloc_status(e);
-    }
-    t->scratch_bytes = need;
-    return NTK_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -178,7 +146,7 @@ int ntk_kmer_table_create(ntk_ctx *ctx, uint32_t k, uint32_t path, uint64_t capa
 void ntk_kmer_table_destroy(ntk_kmer_table *t)
 {
     if (!t) return;
-    t->release({t->d_values, t->d_valid16, t->d_rc16, t->d_keys});   // the scratch, then the keys
+    t->release({t->scratch.d_values, t->scratch.d_valid16, t->scratch.d_rc16, t->d_keys});   // the scratch, then the keys
     delete t;
 }
 
@@ -199,17 +167,17 @@ int ntk_kmer_table_count_device(ntk_kmer_table *t, const uint8_t *d_seq, const u
     // chunks of kChunkBases; each chunk after the first is materialised from `halo` bytes before its start (a multiple of 16: d_seq
     // stays aligned; >= k - 1: every window that ends in the chunk is whole), and only windows ending at or after the start count
     const uint64_t halo = ((uint64_t)t->k - 1 + 15) & ~(uint64_t)15;
-    int rc = ensure_scratch(t, (n_bytes < kChunkBases ? n_bytes : kChunkBases) + (n_bytes > kChunkBases ? halo : 0));
+    int rc = t->scratch.ensure(t->stream, (n_bytes < kChunkBases ? n_bytes : kChunkBases) + (n_bytes > kChunkBases ? halo : 0));
     if (rc) return rc;
     for (uint64_t start = 0; start < n_bytes; start += kChunkBases) {
         const uint64_t end = n_bytes - start > kChunkBases ? start + kChunkBases : n_bytes;
         const uint64_t base = start ? start - halo : 0, len = end - base;
-        rc = ntk_materialize_device_quality(t->ctx, d_seq + base, d_qual ? d_qual + base : nullptr, len, p, t->d_values,
-                                            t->d_valid16, t->d_rc16);
+        rc = ntk_materialize_device_quality(t->ctx, d_seq + base, d_qual ? d_qual + base : nullptr, len, p, t->scratch.d_values,
+                                            t->scratch.d_valid16, t->scratch.d_rc16);
         if (rc) return rc;
         CT_HIPCHK(hipSetDevice(t->device));
         InsertArgs a;
-        a.values = t->d_values; a.valid16 = t->d_valid16;
+        a.values = t->scratch.d_values; a.valid16 = t->scratch.d_valid16;
         a.first = start - base; a.n = len;
         a.keys = t->d_keys; a.counts = t->d_counts; a.stats = t->d_stats;
         a.mask = t->slots - 1; a.probe_max = t->probe_max;

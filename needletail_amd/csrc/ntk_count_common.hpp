@@ -1,6 +1,8 @@
 // What the two count tables share (ntk_count.hip: k <= 32, one key word; ntk_wide_count.hip: k = 33..63, two key words): the
 // constants, the hash, the wave and block sums, the extract count / scan and spectrum kernels, and TableCore, the host side of a table
-// apart from its key words.  The read-side kernels see a table as its occupancy words (`occ`: the narrow keys, the wide hi; EMPTY =
+// apart from its key words, and the scratch of the materialise face, which the sketch (ntk_sketch.hip) takes from here as well, with
+// the hash and the sums (it defines NTK_COUNT_COMMON_NO_TABLE first: no table kernel, no TableCore, so its library ships none of
+// them).  The read-side kernels see a table as its occupancy words (`occ`: the narrow keys, the wide hi; EMPTY =
 // free) and its counts.  Everything is in an anonymous namespace, so each library keeps a private copy and exports nothing new.
 // DESIGN.md sections 10 and 11.
 #pragma once
@@ -61,6 +63,7 @@ __device__ inline uint32_t block_sum_u32(uint32_t v, uint32_t *lds)
     return s;
 }
 
+#ifndef NTK_COUNT_COMMON_NO_TABLE
 // extract, step 1: occupied slots with count >= min_count, per block of kExtractPerBlock slots
 __global__ __launch_bounds__(kThreads) void ct_extract_count_kernel(const uint64_t *occ, const uint64_t *counts, uint64_t slots,
                                                                     uint64_t min_count, uint32_t *block_counts)
@@ -114,6 +117,8 @@ __global__ __launch_bounds__(kThreads) void ct_spectrum_kernel(const uint64_t *o
         if (bins[b]) add_agent(hist + b, bins[b]);
 }
 
+#endif  // NTK_COUNT_COMMON_NO_TABLE
+
 inline unsigned grid_for(uint64_t items, unsigned block, unsigned cap)
 {
     const uint64_t b = (items + block - 1) / block;
@@ -126,6 +131,40 @@ int alloc_status(hipError_t e)
     return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? NTK_ERR_NOMEM : NTK_ERR_HIP;
 }
 
+// The scratch of one chunk of the core's materialise face (values, valid plane, strand plane: 10 B per base), grown on demand.  Owned by
+// whatever consumes that face chunk by chunk: the narrow table and the sketch (ntk_sketch.hip).
+struct MaterialiseScratch {
+    uint64_t bytes = 0;   // bases it holds (a multiple of 16)
+    uint64_t *d_values = nullptr;
+    uint16_t *d_valid16 = nullptr, *d_rc16 = nullptr;
+
+    void release()
+    {
+        if (d_values) (void)hipFree(d_values);
+        if (d_valid16) (void)hipFree(d_valid16);
+        if (d_rc16) (void)hipFree(d_rc16);
+        d_values = nullptr; d_valid16 = d_rc16 = nullptr; bytes = 0;
+    }
+
+    int ensure(hipStream_t stream, uint64_t len)
+    {
+        const uint64_t need = (len + 15) & ~(uint64_t)15;
+        if (need <= bytes) return NTK_OK;
+        CT_HIPCHK(hipStreamSynchronize(stream));   // the old scratch may still be read by queued kernels
+        release();
+        hipError_t e;
+        if ((e = hipMalloc((void **)&d_values, need * sizeof(uint64_t))) != hipSuccess ||
+            (e = hipMalloc((void **)&d_valid16, need / 16 * sizeof(uint16_t))) != hipSuccess ||
+            (e = hipMalloc((void **)&d_rc16, need / 16 * sizeof(uint16_t))) != hipSuccess) {
+            release();
+            return alloc_status(e);
+        }
+        bytes = need;
+        return NTK_OK;
+    }
+};
+
+#ifndef NTK_COUNT_COMMON_NO_TABLE
 // The host side of a table apart from its key words, which the table adds (keys; hi, lo) and hands to the helpers that set up, clear
 // or free every slot array.  `stat_words`: the length of the table's stats array.
 struct TableCore {
@@ -273,5 +312,6 @@ struct TableCore {
         return NTK_OK;
     }
 };
+#endif  // NTK_COUNT_COMMON_NO_TABLE
 
 }  // namespace

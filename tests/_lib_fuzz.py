@@ -1,0 +1,605 @@
+"""A seeded, structured, differential fuzz of the six k-mer libraries (count table, wide count table, HyperLogLog sketch, read
+abundance, read trimmer with its batch writer, MinHash) against the host models the suite already has.  Shared by
+tests/test_lib_fuzz_inputs.py (CPU: the slices are not vacuous), tests/test_gpu_lib_fuzz.py (the fixed slices) and tools/lib_fuzz.py
+(time-budgeted runs, replay, dump).  Importable without a GPU: torch is imported only inside the device functions.
+
+Truth is the existing models only: `_count_helpers.oracle_values` / `oracle_items`, `test_gpu_wide_count.oracle_items`,
+`_sketch_model`, `_minhash_model`, `_abundance_model`, `_trim_model`.  Every comparison is `array_equal` / `==`.
+
+The generator (`make_case`).  Query records and a related reference set (the table's batch) are sampled from one random genome of a
+few kb with substitution errors, at different and uneven coverage, plus foreign reads and exact duplicates, so that abundances
+differ along a record.  Record content kinds are those of tools/gpu_fuzz.py's make_input (KINDS); record lengths come from EDGE
+lengths derived from the kernels' constants (`edge_lengths`).
+
+Excluded inputs (what a header rules out is not generated for that stage):
+  * bytes of the pre-step's "deleted" class inside a record - needletail_amd.h, "Device batch layout: ... no bytes of the pre-step's
+    'deleted' class inside a record (the packer, ntk_batch_append, removed them)": none for PRE_NONE, CR / LF for PRE_STRIP_RETURNS,
+    space / tab / CR / LF for PRE_NORMALIZE*; `junk_bytes(pre)` leaves them out.  The records' own break byte is the packer's '\\n';
+  * PATH_BYTES_CANONICAL with PRE_NONE / PRE_STRIP_RETURNS - needletail_amd_count.h, _abundance.h, _trim.h, _minhash.h: "Byte-path
+    input that was not normalised ... is NTK_ERR_UNSUPPORTED": `_count_helpers.PATH_PRES` has no such pair;
+  * k = 33..63 on a bit path, and on the abundance and trim libraries - needletail_amd_abundance.h / _trim.h: "k = 33..63 ... is not
+    served here"; the wide stages draw PATH_BYTES_CANONICAL with PRE_NORMALIZE / PRE_NORMALIZE_IUPAC only;
+  * offsets that are not the packer's - needletail_amd_abundance.h: "d_offsets[0] = 0, d_offsets[n_records] = n_bytes, record r = the
+    bytes [d_offsets[r], d_offsets[r + 1]) whose last byte is the record's break byte": offsets are always `_trim_model.offsets`;
+  * a foreign MinHash sketch coarser than the handle - needletail_amd_minhash.h: "The counts stay exact when the other sketch keeps
+    at least what this one would: the same num or a larger one, the same scaled or a divisor of it".
+The 64 Mi-base chunk seams and batches above 2^32 bytes stay with the tests that own them."""
+import numpy as np
+
+import needletail_amd as nt
+import _abundance_model as A
+import _minhash_model as M
+import _sketch_model as S
+import _trim_model as T
+from _count_helpers import M64, PATH_PRES, oracle_items, oracle_values, pack, quality_masked, upload
+
+BYTES, BITS, BITS_CANON = nt.PATH_BYTES_CANONICAL, nt.PATH_BITS, nt.PATH_BITS_CANONICAL
+STAGES = ("count", "count_wide", "minhash", "minhash_wide", "abundance", "trim")
+WIDE_STAGES = ("count_wide", "minhash_wide")
+KS = (1, 2, 3, 15, 16, 17, 21, 31, 32)
+WIDE_KS = (33, 34, 47, 48, 49, 62, 63)
+WIDE_PRES = (nt.PRE_NORMALIZE, nt.PRE_NORMALIZE_IUPAC)
+KINDS = ("clean", "n_runs", "breaks", "mixed", "periodic", "genome")
+KIND_WEIGHTS = (0.10, 0.20, 0.10, 0.15, 0.10, 0.35)   # what the genome covers leads: records that are cut, not dropped whole
+NUMS = (1, 2, 16, 500, 1 << 20)
+SCALEDS = (1, 2, 7, 1000)
+BUFFERS = (64, 65, 100, 256, 4096, 0)
+MIN_COUNTS_ABUNDANCE = (0, 1, 2, 3)
+MIN_COUNTS_TRIM = (1, 2, 3)
+MODES = (T.PREFIX, T.LONGEST)
+
+# the fixed slices of the GPU suite: stage -> (seed, cases).  tests/test_lib_fuzz_inputs.py proves on the CPU that each meets its
+# conditions; the counts are the smallest at which they do (seeds 100..139 were searched per stage)
+SLICES = {"count": (103, 3), "count_wide": (111, 3), "minhash": (134, 8), "minhash_wide": (131, 10), "abundance": (104, 3),
+          "trim": (111, 4)}
+
+LANE_RUN = S.LANE_RUN            # kLaneRun (ntk_wide_count.hip, ntk_sketch.hip, ntk_wide_walk.hpp): window ends per lane
+LONG_PIECES_BYTES = 2048 * 16    # kLongPieces (ntk_trim.hip) 16-byte pieces: beyond it a record goes to rt_copy_long_kernel
+LONG_RECORD = 65536              # kLongRecord (ntk_abundance.hip): more candidate windows go to ra_block_kernel
+TABLE_CAPACITY = 1 << 17         # of the tables a session keeps: above the distinct k-mers of any reference set
+
+ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+COMP = np.arange(256, dtype=np.uint8)
+for _a, _b in zip(b"ACGTacgt", b"TGCAtgca"):
+    COMP[_a] = _b
+UNITS = (b"A", b"AT", b"GC", b"ACGT", b"AATT", b"ACGTACGTTGCA")
+JUNK = b"NnRYKMSWBDHVrykm-.*\x00\x7f\x80\xff0@>+"
+WHITESPACE = b" \t\r\n"
+DELETED = {nt.PRE_NONE: b"", nt.PRE_STRIP_RETURNS: b"\r\n", nt.PRE_NORMALIZE: WHITESPACE, nt.PRE_NORMALIZE_IUPAC: WHITESPACE}
+
+
+def edge_lengths(k: int) -> dict:
+    """name -> record length L, each from a constant of the kernels (w = candidate windows, L = w + k - 1)."""
+    e = {
+        "0": 0, "1": 1,                                       # the empty record (one break byte) and the shortest one
+        "k-2": max(k - 2, 0), "k-1": k - 1,                   # no window
+        "k": k, "k+1": k + 1, "2k-1": 2 * k - 1, "2k": 2 * k,  # one, two, k and k + 1 windows: a break in the middle leaves none / one
+    }
+    for L in (15, 16, 17):        # the core's 16-base lane and the copy kernels' 16-byte piece (kCopyGroup pieces of 16 B)
+        e[str(L)] = L
+    for L in (63, 64, 65):        # one 64-bit plane word of rt_solid_kernel; kLaneRun / kPrime of the wide walkers
+        e[str(L)] = L
+    for L in (127, 128, 129):     # two plane words; two lane runs
+        e[str(L)] = L
+    for w in (191, 192, 193):     # kRegWindows = 64 * kRegRounds of ntk_abundance.hip: the register path and the streamed one
+        e[f"w{w}"] = w + k - 1
+    for w in (255, 256, 257):     # kWaveInFlight * 64 of ntk_abundance.hip, and rt_solid_kernel's tile 64 * kSolidRounds
+        e[f"w{w}"] = w + k - 1
+    for L in (511, 512, 513):     # 32 sixteen-bit words of the materialise face's valid plane
+        e[f"L{L}"] = L
+    for w in (2047, 2048, 2049):  # kGroup * kGroupRounds = 32 plane words of 64 window ends: the lane group and the whole wave
+        e[f"w{w}"] = w + k - 1
+    return e
+
+
+LONG_CLASSES = ("long_pieces", "long_record")   # kLongPieces * 16 bytes +- 17; kLongRecord + k - 1 +- 1 bases
+
+
+def junk_bytes(pre: int) -> np.ndarray:
+    """Non-base bytes a record may hold under `pre`: everything of gpu_fuzz's JUNK and the whitespace the pre-step does not delete."""
+    ws = bytes(b for b in WHITESPACE if b not in DELETED[pre])
+    return np.frombuffer(JUNK + ws, dtype=np.uint8)
+
+
+class Case:
+    """records / quals / qbreaks (the quality byte under each record's break byte) / cutoff: the query batch.  ref_records: the batch
+    the table counts.  kinds / classes / starts: per record, its content kind, its edge-length class (None: a random length) and
+    its first byte's offset in the packed batch."""
+
+    def __init__(self, k, path, pre):
+        self.k, self.path, self.pre = k, path, pre
+        self.records, self.quals, self.qbreaks, self.kinds, self.classes = [], [], [], [], []
+        self.cutoff, self.ref_records = 0, []
+
+    # packed forms ------------------------------------------------------------------------------------------------------------------
+    def buf(self) -> bytes:
+        return pack(self.records)
+
+    def offsets(self) -> np.ndarray:
+        return T.offsets(self.records)
+
+    def qual_stream(self) -> np.ndarray:
+        return stream(self.quals, self.qbreaks)
+
+    def starts(self) -> np.ndarray:
+        return self.offsets()[:-1].astype(np.int64)
+
+    def tag(self) -> str:
+        return f"k {self.k} path {self.path} pre {self.pre} cutoff {self.cutoff} records {len(self.records)} bytes {len(self.buf())}"
+
+
+def stream(quals, qbreaks) -> np.ndarray:
+    """The parallel stream of a packed batch: each record's bytes, then the byte under its break byte."""
+    if not quals:
+        return np.zeros(0, dtype=np.uint8)
+    return np.concatenate([np.append(np.frombuffer(bytes(q), dtype=np.uint8), np.uint8(b)) for q, b in zip(quals, qbreaks)]).astype(np.uint8)
+
+
+def _genome_read(rng, genome, L, err=0.01):
+    n = len(genome)
+    if L <= n:
+        s = min(int(rng.random() ** 2 * (n - L + 1)), n - L)   # uneven coverage: the genome's head is sampled more often
+        r = genome[s:s + L].copy()
+    else:
+        r = np.resize(np.roll(genome, -int(rng.integers(0, n))), L).copy()
+    sub = rng.random(L) < err
+    r[sub] = ACGT[rng.integers(0, 4, int(sub.sum()))]
+    if rng.random() < 0.3:
+        r = COMP[r[::-1]]
+    return r
+
+
+def _content(rng, kind, L, k, pre, genome, at0, wide):
+    """One record of `kind` and length L whose first byte lies at batch offset at0."""
+    if L == 0:
+        return np.zeros(0, dtype=np.uint8)
+    if kind == "clean":
+        return ACGT[rng.integers(0, 4, L)].copy()
+    if kind == "periodic":
+        a = np.resize(np.frombuffer(UNITS[int(rng.integers(0, len(UNITS)))], dtype=np.uint8), L).copy()
+        for _ in range(int(rng.integers(0, 4))):
+            a[int(rng.integers(0, L))] = ACGT[int(rng.integers(0, 4))]
+        return a
+    a = _genome_read(rng, genome, L)
+    junk = junk_bytes(pre)
+    if kind == "n_runs":       # runs of N of length k - 3 .. k + 3, at random places and at multiples of 16 and 64 +- 1 of the batch
+        for _ in range(int(rng.integers(1, 2 + L // 150))):
+            ln = max(1, k + int(rng.integers(-3, 4)))
+            at = int(rng.integers(0, L))
+            u = rng.random()
+            if u < 0.35:
+                at = (at0 + at) // 16 * 16 + int(rng.integers(-1, 2)) - at0
+            elif u < 0.7:
+                at = (at0 + at) // 64 * 64 + int(rng.integers(-1, 2)) - at0
+            at = min(max(at, 0), L - 1)
+            a[at:at + ln] = ord("N")
+    elif kind == "breaks":     # a single break every k - 1 / k / k + 1 bases: no, one or two windows between breaks
+        step = max(1, k + int(rng.integers(-1, 2)))
+        a[step - 1::step + 1] = junk[int(rng.integers(0, junk.size))] if rng.random() < 0.5 else ord("N")
+    elif kind == "mixed":      # lower case, U / u, IUPAC, whitespace the pre-step keeps, the junk bytes
+        m = rng.random(L)
+        a[m < 0.15] |= 0x20
+        sel = m > 0.96
+        a[sel] = junk[rng.integers(0, junk.size, int(sel.sum()))]
+        us = (m > 0.94) & (m <= 0.96)
+        a[us] = np.frombuffer(b"Uu", dtype=np.uint8)[rng.integers(0, 2, int(us.sum()))]
+    if wide and kind != "genome" and rng.random() < 0.5:
+        # k = 33..63: one more break within k - 1 bytes after a lane-run boundary of the batch, or one byte before it
+        b = (at0 + int(rng.integers(0, L))) // LANE_RUN * LANE_RUN + int(rng.integers(-1, k)) - at0
+        if 0 <= b < L:
+            a[b] = ord("N")
+    return a
+
+
+def _qualities(rng, L, cutoff, rate):
+    """Most bytes at the cutoff, a share `rate` one below it (masked: the compare is <), a tenth one above."""
+    c = cutoff if cutoff else 40
+    u = rng.random(L)
+    q = np.full(L, c, dtype=np.uint8)
+    q[u < rate] = c - 1
+    q[u > 0.9] = c + 1
+    return q
+
+
+def make_case(rng, k, path, pre, budget=None, allow_long=True) -> Case:
+    """One case for (k, path, pre).  See the module docstring."""
+    wide = k > 32
+    c = Case(k, path, pre)
+    c.cutoff = 0 if rng.random() < 0.15 else int(rng.integers(33, 76))
+    rate = float(rng.choice([0.002, 0.01, 0.05]))
+    genome = ACGT[rng.integers(0, 4, int(rng.integers(2000, 4001)))]
+    edges = edge_lengths(k)
+    names = list(edges)
+    budget = int(rng.integers(6000, 20001)) if budget is None else budget
+    plan = []   # (class, L)
+    if allow_long and rng.random() < 0.3:
+        plan.append(("long_pieces", LONG_PIECES_BYTES + int(rng.integers(-17, 18))))
+    if allow_long and rng.random() < 0.12:
+        plan.append(("long_record", LONG_RECORD + k - 1 + int(rng.integers(-1, 2))))
+    used = 0
+    while used < budget:
+        if rng.random() < 0.6:
+            name = names[int(rng.integers(0, len(names)))]
+            plan.append((name, edges[name]))
+        else:
+            plan.append((None, int(rng.integers(0, 400))))
+        used += plan[-1][1] + 1
+    order = rng.permutation(len(plan))
+    at = 0
+    for i in order:
+        cls, L = plan[i]
+        if rng.random() < 0.25:
+            # a spacer record of N that puts the next record's first byte where a kernel's geometry changes: around a lane-run
+            # boundary (k = 33..63: 64m - 1 .. 64m + k - 1), or on a drawn residue of the 16-byte copy piece
+            target = int(rng.integers(-1, k)) % LANE_RUN if wide else int(rng.integers(0, 16))
+            pad = (target - at - 1) % (LANE_RUN if wide else 16)
+            _append(c, rng, np.full(pad, ord("N"), dtype=np.uint8), "spacer", None, rate)
+            at += pad + 1
+        kind = KINDS[int(rng.choice(len(KINDS), p=KIND_WEIGHTS))]
+        if cls in LONG_CLASSES and kind in ("clean", "periodic"):
+            kind = "genome"   # a long record of foreign or one-key content says nothing about abundance and costs a hot key
+        _append(c, rng, _content(rng, kind, L, k, pre, genome, at, wide), kind, cls, rate)
+        at += L + 1
+    # the reference set: other reads of the same genome at another coverage, a few foreign reads, exact duplicates of query records,
+    # a periodic read per unit now and then (hot keys the table holds), and T^40 at k = 32 (the key the table keeps in a side word)
+    for _ in range(int(rng.integers(40, 200))):
+        c.ref_records.append(_genome_read(rng, genome, int(rng.integers(50, 251))).tobytes())
+    for _ in range(3):
+        c.ref_records.append(ACGT[rng.integers(0, 4, int(rng.integers(40, 200)))].tobytes())
+    short = [r for r in c.records if len(r) <= 600]
+    for _ in range(min(3, len(short))):
+        c.ref_records.append(short[int(rng.integers(0, len(short)))])
+    for unit in UNITS:
+        if rng.random() < 0.5:
+            c.ref_records.append(bytes(np.resize(np.frombuffer(unit, dtype=np.uint8), 2 * k + int(rng.integers(0, 30)))))
+    if k == 32 and rng.random() < 0.5:
+        c.ref_records.append(b"T" * 40)
+    return c
+
+
+def _append(c, rng, a, kind, cls, rate):
+    c.records.append(a.tobytes())
+    c.quals.append(_qualities(rng, len(a), c.cutoff, rate))
+    c.qbreaks.append(int(rng.integers(0, 256)))   # the byte under a break byte is ignored, whatever it is
+    c.kinds.append(kind)
+    c.classes.append(cls)
+
+
+def draw_params(rng, stage):
+    if stage in WIDE_STAGES:
+        return int(rng.choice(WIDE_KS)), BYTES, int(rng.choice(WIDE_PRES))
+    path, pre = PATH_PRES[int(rng.integers(0, len(PATH_PRES)))]
+    return int(rng.choice(KS)), path, pre
+
+
+def case_rng(seed, stage, it):
+    """The generator of case `it` of a stage: a stream of its own, so that a replay of case N needs no earlier case."""
+    return np.random.default_rng([int(seed), STAGES.index(stage), int(it)])
+
+
+def draw_case(seed, stage, it):
+    """(rng, case) of iteration `it`: the rng has made the case and goes on to the checker's own draws."""
+    rng = case_rng(seed, stage, it)
+    k, path, pre = draw_params(rng, stage)
+    return rng, make_case(rng, k, path, pre)
+
+
+# ---- the models' side -------------------------------------------------------------------------------------------------------------------
+
+def wide_items(buf: bytes, k: int):
+    from test_gpu_wide_count import oracle_items as wide_oracle_items   # (its module imports torch)
+    return wide_oracle_items(buf, k)
+
+
+def oracle_keys(buf: bytes, k: int, path: int, pre: int) -> np.ndarray:
+    """Every key the batch emits, with repeats: narrow values, or [hi, lo] rows at k >= 33."""
+    if k <= 32:
+        return oracle_values(buf, k, path, pre)
+    keys, counts = wide_items(buf, k)
+    return np.repeat(keys, counts, axis=0)
+
+
+def items_of(buf: bytes, k: int, path: int, pre: int):
+    return oracle_items(buf, k, path, pre) if k <= 32 else wide_items(buf, k)
+
+
+def masked_buf(case, use_q: bool) -> bytes:
+    return quality_masked(case.buf(), case.qual_stream(), case.cutoff) if use_q else case.buf()
+
+
+def draw_minhash(rng):
+    """(kind, buffer_entries, use_q, pieces, ops, reset_after) of a MinHash case: the checker's draws, in one place for the CPU test."""
+    kind = dict(num=int(rng.choice(NUMS))) if rng.random() < 0.5 else dict(scaled=int(rng.choice(SCALEDS)))
+    buffer_entries = int(rng.choice(BUFFERS))
+    use_q = bool(rng.random() < 0.5)
+    pieces = int(rng.integers(1, 6))
+    ops = [("stats", "hashes", "nothing", "merge")[int(rng.integers(0, 4))] for _ in range(pieces)]
+    reset_after = int(rng.integers(0, pieces)) if rng.random() < 0.25 else -1
+    return kind, buffer_entries, use_q, pieces, ops, reset_after
+
+
+def draw_trim(rng, k):
+    """(mode, min_count, min_length) of the setting whose rows a trim case compacts and feeds back."""
+    return int(rng.choice(MODES)), int(rng.choice(MIN_COUNTS_TRIM)), int(rng.choice([0, k, 2 * k]))
+
+
+def finer(rng, kind) -> dict:
+    """The same rule or a finer one: a sketch that keeps at least what `kind` would (the header's condition for an exact merge)."""
+    if "num" in kind:
+        return dict(num=min(kind["num"] * int(rng.choice([1, 2, 5])), M.MAX_NUM))
+    return dict(scaled=int(rng.choice([d for d in (1, 2, 7, 500, 1000) if kind["scaled"] % d == 0])))
+
+
+def split_records(case, pieces: int):
+    """The records in `pieces` runs; each run but the last is followed by empty records (single break bytes) up to the next multiple
+    of 16, so that every call starts 16-byte aligned on a record boundary (test_gpu_minhash's _cuts, made to order).  Returns the
+    packed buffer, the quality stream and the cut points."""
+    n = len(case.records)
+    bounds = sorted({n * j // pieces for j in range(1, pieces)} - {0, n})
+    seq, qual, cuts = bytearray(), bytearray(), [0]
+    qs = case.qual_stream().tobytes()
+    off = case.offsets()
+    for i in range(n):
+        if i in bounds:
+            pad = -len(seq) % 16
+            seq += b"\n" * pad
+            qual += b"\x00" * pad
+            cuts.append(len(seq))
+        seq += case.records[i] + b"\n"
+        qual += qs[int(off[i]):int(off[i + 1])]
+    cuts.append(len(seq))
+    return bytes(seq), np.frombuffer(bytes(qual), dtype=np.uint8), cuts
+
+
+# ---- the device side --------------------------------------------------------------------------------------------------------------------
+
+class Session:
+    """What outlives a case: the context, and per (k, path) one table with its abundance and trim handles, whose scratch grows and
+    shrinks from case to case."""
+
+    def __init__(self, ctx):
+        self.ctx, self.handles = ctx, {}
+
+    def table(self, k, path):
+        if (k, path) not in self.handles:
+            t = nt.KmerTable(k, path, TABLE_CAPACITY, self.ctx)
+            self.handles[(k, path)] = (t, nt.ReadAbundance(t), nt.ReadTrimmer(t))
+        return self.handles[(k, path)]
+
+    def counted(self, case):
+        """The session's table of (k, path) after it counted the case's reference set, its handles, and the oracle's items."""
+        t, ra, rt = self.table(case.k, case.path)
+        buf = pack(case.ref_records)
+        t.reset()
+        t.count_device(upload(buf), len(buf), case.pre)
+        self.ctx.synchronize()
+        return t, ra, rt, oracle_items(buf, case.k, case.path, case.pre)
+
+    def close(self):
+        for t, ra, rt in self.handles.values():
+            rt.close(); ra.close(); t.close()
+        self.handles = {}
+
+
+class Mismatch(AssertionError):
+    pass
+
+
+def _eq(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    if got.shape != want.shape or not np.array_equal(got, want):
+        where = ""
+        if got.shape == want.shape and got.size:
+            bad = np.argwhere(got != want)[0].tolist()
+            where = f"; first at {bad}: got {got[tuple(bad)]}, want {want[tuple(bad)]}"
+        raise Mismatch(f"{what}: shapes {got.shape} / {want.shape}{where}")
+
+
+def _dev_u64(a):
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).copy()).cuda()
+    torch.cuda.synchronize()
+    return t
+
+
+def _host(t) -> np.ndarray:
+    a = t.cpu().numpy()
+    return a.view(np.uint64) if a.dtype == np.int64 else a
+
+
+def check_count(sess, case, rng):
+    """KmerSketch registers and n_windows, then items, stats, spectrum and lookups of the table the sketch sizes."""
+    k, path, pre = case.k, case.path, case.pre
+    buf = case.buf()
+    fill = ord("A") if rng.random() < 0.5 else ord("\n")   # readable padding of bases past n_bytes is not input
+    dev, dq = upload(buf, fill=fill), upload(case.qual_stream().tobytes(), fill=0xFF)
+    ref_keys = items_of(pack(case.ref_records), k, path, pre)[0]
+    for use_q in (False, True):
+        what = f"count quality {use_q}"
+        kw = dict(d_qual=dq, quality_cutoff=case.cutoff) if use_q else {}
+        keys = oracle_keys(masked_buf(case, use_q), k, path, pre)
+        want = np.unique(keys, axis=0, return_counts=True) if keys.shape[0] else (keys, np.zeros(0, dtype=np.int64))
+        with nt.KmerSketch(k, path, sess.ctx) as sk:
+            sk.add_device(dev, len(buf), pre, **kw)
+            _eq(sk.registers(), S.registers(keys), what + " registers")
+            _eq(sk.estimate()["n_windows"], keys.shape[0], what + " n_windows")
+            with sk.table() as t:
+                t.count_device(dev, len(buf), pre, **kw)
+                got = t.items()
+                _eq(got[0], want[0], what + " keys")
+                _eq(got[1], want[1].astype(np.uint64), what + " counts")
+                st = t.stats()
+                _eq([st["n_distinct"], st["n_total"], st["n_dropped"]], [len(want[0]), int(want[1].sum()), 0], what + " stats")
+                _eq(t.spectrum(64), np.bincount(np.minimum(want[1], 63), minlength=64).astype(np.uint64), what + " spectrum")
+                # present keys, keys of the reference set (present or absent), and the all-T key
+                q = np.concatenate([want[0][::3], ref_keys[: 4000]])
+                if k == 32 and path == BITS:
+                    q = np.concatenate([q, np.array([M64], dtype=np.uint64)])
+                if q.shape[0]:
+                    _eq(t.lookup(q), _lookup(q, want), what + " lookup")
+
+
+def _lookup(q, items):
+    """Counts of the queried keys in the oracle's items (absent = 0): `_abundance_model.lookup`, on [hi, lo] rows through a dict."""
+    if q.ndim == 1:
+        return A.lookup(q, (items[0], items[1].astype(np.uint64)))
+    d = {(int(h), int(lo)): int(c) for (h, lo), c in zip(items[0], items[1])}
+    return np.array([d.get((int(h), int(lo)), 0) for h, lo in q], dtype=np.uint64)
+
+
+def _assert_minhash(mh, keys, kind, first, what):
+    want = M.sketch(keys, **kind)
+    if first == "stats":
+        st, (h, c) = mh.stats(), mh.hashes()
+    else:
+        (h, c), st = mh.hashes(), mh.stats()
+    _eq(h, want[0], what + " hashes")
+    _eq(c, want[1], what + " counts")
+    _eq([st["n_windows"], st["n_kept"], st["threshold"]], [keys.shape[0], want[0].size, M.threshold(want[0], **kind)], what + " stats")
+
+
+def check_minhash(sess, case, rng):
+    """One handle through 1..5 add_device calls with stats / hashes / nothing / merge between them, now and then a reset."""
+    k, path, pre = case.k, case.path, case.pre
+    kind, buffer_entries, use_q, pieces, ops, reset_after = draw_minhash(rng)
+    other = make_case(rng, k, path, pre, budget=int(rng.integers(200, 3000)), allow_long=False)
+    what = f"minhash {kind} buffer {buffer_entries} quality {use_q} pieces {pieces} ops {ops} reset_after {reset_after}"
+    buf, qual, cuts = split_records(case, pieces)
+    dev, dq = upload(buf, fill=ord("A")), upload(qual.tobytes(), fill=0xFF)
+    masked = quality_masked(buf, qual, case.cutoff) if use_q else buf
+    empty = np.zeros((0,) if k <= 32 else (0, 2), dtype=np.uint64)
+    with nt.KmerMinHash(k, path, ctx=sess.ctx, buffer_entries=buffer_entries, **kind) as mh:
+        keys = [empty]
+        i = 0
+        while i < len(cuts) - 1:
+            a, b = cuts[i], cuts[i + 1]
+            kw = dict(d_qual=dq.data_ptr() + a, quality_cutoff=case.cutoff) if use_q else {}
+            mh.add_device(dev.data_ptr() + a, b - a, pre, **kw)
+            keys.append(oracle_keys(masked[a:b], k, path, pre))
+            op = ops[i]
+            if op == "merge":
+                okind = finer(rng, kind)
+                obuf = other.buf()
+                okeys = oracle_keys(obuf, k, path, pre)
+                with nt.KmerMinHash(k, path, ctx=sess.ctx, buffer_entries=int(rng.choice(BUFFERS)), **okind) as mo:
+                    mo.add_device(upload(obuf), len(obuf), pre)
+                    _assert_minhash(mo, okeys, okind, "hashes", what + f" other {okind}")
+                    if rng.random() < 0.5:
+                        mh.merge(mo)
+                    else:
+                        h, c = mo.hashes()
+                        mh.merge(h, c, n_windows=okeys.shape[0])
+                keys.append(okeys)
+            if op != "nothing":
+                _assert_minhash(mh, np.concatenate(keys), kind, "stats" if op == "stats" else "hashes", what + f" after piece {i} {op}")
+            if i == reset_after:
+                mh.reset()
+                keys, reset_after, i = [empty], -1, 0   # start over: the handle is as new
+                continue
+            i += 1
+        _assert_minhash(mh, np.concatenate(keys), kind, "hashes", what + " at the end")
+    return what
+
+
+def check_abundance(sess, case, rng):
+    """Rows for min_count 0..3 with and without the quality stream, then a shorter batch and the whole one again on the same handle."""
+    k, path, pre = case.k, case.path, case.pre
+    t, ra, rt, items = sess.counted(case)
+    buf, off = case.buf(), case.offsets()
+    n = len(case.records)
+    dev, dq, d_off = upload(buf), upload(case.qual_stream().tobytes(), fill=0xFF), _dev_u64(off)
+    for use_q in (False, True):
+        kw = dict(d_qual=dq, quality_cutoff=case.cutoff) if use_q else {}
+        values = [A.record_values(r, k, path, pre, case.quals[i] if use_q else None, case.cutoff) for i, r in enumerate(case.records)]
+        for mc in MIN_COUNTS_ABUNDANCE:
+            want = A.rows_from_values(values, items, mc)
+            _eq(_host(ra.run_device(dev, len(buf), d_off, n, pre, min_count=mc, **kw)), want, f"abundance quality {use_q} min_count {mc}")
+        m = int(rng.integers(0, n + 1))   # a prefix of the batch: the scratch shrinks; the bytes after it are readable and not input
+        if m:
+            got = _host(ra.run_device(dev, int(off[m]), d_off, m, pre, min_count=2, **kw))
+            _eq(got, A.rows_from_values(values[:m], items, 2), f"abundance quality {use_q} first {m} records")
+    if rng.random() < 0.3:
+        ra.trim()
+
+
+def check_trim(sess, case, rng):
+    """Rows of both modes, the compaction with the quality bytes as the parallel stream, and the compacted device tensors handed
+    unchanged to a fresh count table, the abundance call and the trimmer again."""
+    k, path, pre, cutoff = case.k, case.path, case.pre, case.cutoff
+    t, ra, rt, items = sess.counted(case)
+    recs, buf, off = case.records, case.buf(), case.offsets()
+    n = len(recs)
+    qs = case.qual_stream()
+    dev, dq, d_off = upload(buf), upload(qs.tobytes(), fill=0xFF), _dev_u64(off)
+    for use_q in (False, True):
+        kw = dict(d_qual=dq, quality_cutoff=cutoff) if use_q else {}
+        wins = [T.record_windows(r, k, path, pre, case.quals[i] if use_q else None, cutoff) for i, r in enumerate(recs)]
+        for mode in MODES:
+            for mc in MIN_COUNTS_TRIM:
+                for ml in (0, k, 2 * k):
+                    want = T.rows_from_windows(recs, wins, items, k, mode, mc, ml)
+                    got = rt.run_device(dev, len(buf), d_off, n, pre, min_count=mc, mode=mode, min_length=ml, **kw)
+                    _eq(_host(got), want, f"trim quality {use_q} mode {mode} min_count {mc} min_length {ml}")
+    # the compaction of one drawn setting (rows with the quality mask, whose windows are still in `wins`)
+    mode, mc, ml = draw_trim(rng, k)
+    what = f"trim round trip mode {mode} min_count {mc} min_length {ml}"
+    want_rows = T.rows_from_windows(recs, wins, items, k, mode, mc, ml)
+    d_rows = rt.run_device(dev, len(buf), d_off, n, pre, min_count=mc, mode=mode, min_length=ml, d_qual=dq, quality_cutoff=cutoff)
+    want = T.compact(recs, want_rows, case.quals, case.qbreaks)
+    out = rt.compact_device(dev, len(buf), d_off, n, d_rows, dq)
+    pad = len(want[0])
+    _eq(out[1], want[1], what + " n_bytes")
+    _eq(_host(out[0])[:pad], np.frombuffer(want[0], dtype=np.uint8), what + " bytes and padding")
+    _eq(_host(out[2]), want[2], what + " offsets")
+    _eq(_host(out[3]), want[3], what + " sources")
+    _eq(_host(out[4])[:pad], np.frombuffer(want[4], dtype=np.uint8), what + " aux bytes and padding")
+    n_out = len(want[3])
+    if n_out == 0:
+        return what
+    # the model's compacted records; the device tensors go on as they are
+    src = [int(s) for s in want[3]]
+    o_recs = [recs[s][int(want_rows[s][0]):int(want_rows[s][0] + want_rows[s][1])] for s in src]
+    o_quals = [case.quals[s][int(want_rows[s][0]):int(want_rows[s][0] + want_rows[s][1])] for s in src]
+    o_buf, o_qs = pack(o_recs), stream(o_quals, [case.qbreaks[s] for s in src])
+    assert o_buf == want[0][:want[1]]
+    with nt.KmerTable(k, path, max(want[1], 16), sess.ctx) as fresh:
+        fresh.count_device(out[0], out[1], pre, d_qual=out[4], quality_cutoff=cutoff)
+        w = oracle_items(quality_masked(o_buf, o_qs, cutoff), k, path, pre)
+        got = fresh.items()
+        _eq(got[0], w[0], what + " recount keys")
+        _eq(got[1], w[1].astype(np.uint64), what + " recount counts")
+    _eq(_host(ra.run_device(out[0], out[1], out[2], n_out, pre, d_qual=out[4], quality_cutoff=cutoff, min_count=mc)),
+        A.rows(o_recs, items, k, path, pre, mc, o_quals, cutoff), what + " abundance of the output")
+    _eq(_host(rt.run_device(out[0], out[1], out[2], n_out, pre, d_qual=out[4], quality_cutoff=cutoff, min_count=mc, mode=mode, min_length=ml)),
+        T.rows(o_recs, items, k, path, pre, mode, mc, ml, o_quals, cutoff), what + " trim of the output")
+    if rng.random() < 0.3:
+        rt.release()
+    return what
+
+
+CHECKERS = {"count": check_count, "count_wide": check_count, "minhash": check_minhash, "minhash_wide": check_minhash,
+            "abundance": check_abundance, "trim": check_trim}
+
+
+def run_case(sess, seed, stage, it):
+    """Case `it` of a stage on the device.  A failure carries what the tool needs to replay it."""
+    rng, case = draw_case(seed, stage, it)
+    try:
+        CHECKERS[stage](sess, case, rng)
+    except Exception as e:
+        kinds = sorted(set(case.kinds))
+        raise Mismatch(f"MISMATCH seed {seed} it {it} stage {stage} ({case.tag()} kinds {kinds}): {type(e).__name__}: {e}") from e
+    return case
+
+
+def run_slice(sess, stage):
+    seed, n = SLICES[stage]
+    for it in range(1, n + 1):
+        run_case(sess, seed, stage, it)
+
+
+def dump(case, path):
+    """The case as an .npz: packed query batch, offsets, quality stream, packed reference batch and its offsets, and its parameters."""
+    np.savez(path, seq=np.frombuffer(case.buf(), dtype=np.uint8), offsets=case.offsets(), qual=case.qual_stream(),
+             ref=np.frombuffer(pack(case.ref_records), dtype=np.uint8), ref_offsets=T.offsets(case.ref_records),
+             params=np.array([case.k, case.path, case.pre, case.cutoff]), kinds=np.array(case.kinds))

@@ -185,6 +185,57 @@ def lib() -> C.CDLL:
     return L
 
 
+_loaded = {}
+
+
+def load(path: str, prefix: str, calls: dict, needs=()) -> C.CDLL:
+    """The library at `path`, built on the core's public ABI, with its calls (`prefix` + each name of `calls`) typed; loaded once.
+    `needs`: the lib() of every other library it links against, loaded first, after the core."""
+    if path in _loaded:
+        return _loaded[path]
+    lib()
+    for need in needs:
+        need()
+    if not os.path.exists(path):
+        raise ImportError(f"{path} is missing: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()')")
+    X = C.CDLL(path)
+    for call, argtypes in calls.items():
+        getattr(X, prefix + call).argtypes = argtypes
+    getattr(X, prefix + "destroy").restype = None
+    _loaded[path] = X
+    return X
+
+
+class Handle:
+    """A native handle (_h) behind the calls of one such library: a subclass names the library (_lib, its module's lib(), as a
+    staticmethod) and the symbol prefix (_prefix), and creates the handle."""
+
+    _prefix: str
+
+    def _fn(self, call: str):
+        return getattr(self._lib(), self._prefix + call)
+
+    def _check(self, call: str, *args):
+        check(self._fn(call)(*args), self._prefix + call)
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def strerror(status: int) -> str:
     return lib().ntk_strerror(status).decode()
 

@@ -14,8 +14,8 @@ import numpy as np
 
 from . import _lib as L
 from . import counting
-from .counting import KmerTable
-from .engine import Batch, Context, _ptr
+from .counting import KmerTable, upload_records_with_offsets
+from .engine import _ptr
 from .wide_counting import WideKmerTable
 
 LIB_PATH = os.path.join(L._HERE, "libneedletail_amd_abundance.so")
@@ -34,50 +34,16 @@ CALLS = {
 # every symbol include/needletail_amd_abundance.h declares
 SYMBOLS = [PREFIX + c for c in CALLS]
 
-_abundance_lib = None
-
 
 def lib() -> C.CDLL:
     """The abundance library with its calls typed; loaded once."""
-    global _abundance_lib
-    if _abundance_lib is None:
-        counting.lib()   # the core and the count library first: the abundance library links against both
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()')")
-        X = C.CDLL(LIB_PATH)
-        for call, argtypes in CALLS.items():
-            getattr(X, PREFIX + call).argtypes = argtypes
-        getattr(X, PREFIX + "destroy").restype = None
-        _abundance_lib = X
-    return _abundance_lib
+    return L.load(LIB_PATH, PREFIX, CALLS, needs=(counting.lib,))
 
 
-def upload_records_with_offsets(ctx: Context, records, pre: int):
-    """counting.upload_records with the packer's record offsets: (device batch, n_bytes, device int64 offsets, n_records), or None
-    for no records."""
-    import torch
-    records = list(records)
-    if not records:
-        return None
-    b = Batch(ctx, sum(len(r) for r in records) + len(records), len(records))
-    try:
-        for r in records:
-            if not b.append(bytes(r), pre):
-                raise RuntimeError("batch sized for the records is full")
-        seq, off = b.buffers()
-        n = int(seq.size)
-        device = f"cuda:{ctx.device}"
-        dev = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
-        dev[:n] = torch.from_numpy(np.array(seq, copy=True)).to(device)
-        d_off = torch.from_numpy(np.array(off, copy=True).view(np.int64)).to(device)
-        torch.cuda.synchronize(dev.device)
-    finally:
-        b.release()
-    return dev, n, d_off, len(records)
-
-
-class ReadAbundance:
+class ReadAbundance(L.Handle):
     """Per-record abundance rows against `table`, a KmerTable (k <= 32), which it borrows: keep the table open while this is."""
+
+    _lib, _prefix = staticmethod(lib), PREFIX
 
     def __init__(self, table: KmerTable):
         if isinstance(table, WideKmerTable):
@@ -88,26 +54,6 @@ class ReadAbundance:
         self.k, self.path = table.k, table.path
         self._h = C.c_void_p()
         self._check("create", self.ctx._h, table._h, C.byref(self._h))
-
-    def _check(self, call: str, *args):
-        L.check(getattr(lib(), PREFIX + call)(*args), PREFIX + call)
-
-    def close(self):
-        if self._h:
-            lib().ntk_read_abundance_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def trim(self):
         """Free the scratch kept between calls."""

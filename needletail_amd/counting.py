@@ -2,7 +2,7 @@
 
 KmerTable counts canonical (or forward) k-mers, k <= 32, in a hash table in device memory and answers with the sorted
 (k-mer, count) pairs, the abundance spectrum and point lookups.  There is no fallback: without a gfx950 device every call raises.
-CountTable and load() are what it shares with wide_counting.WideKmerTable (k = 33..63), whose library has the same eight calls under
+CountTable and CALLS are what it shares with wide_counting.WideKmerTable (k = 33..63), whose library has the same eight calls under
 its own symbol prefix."""
 from __future__ import annotations
 
@@ -36,26 +36,9 @@ CALLS = {
 # every symbol include/needletail_amd_count.h declares
 SYMBOLS = [PREFIX + c for c in CALLS]
 
-_libs = {}
-
-
-def load(path: str, prefix: str) -> C.CDLL:
-    """The count table library at `path` with its calls (`prefix` + CALLS) typed; loaded once."""
-    if prefix in _libs:
-        return _libs[prefix]
-    L.lib()   # the core library first: the count libraries link against it
-    if not os.path.exists(path):
-        raise ImportError(f"{path} is missing: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()')")
-    X = C.CDLL(path)
-    for call, argtypes in CALLS.items():
-        getattr(X, prefix + call).argtypes = argtypes
-    getattr(X, prefix + "destroy").restype = None
-    _libs[prefix] = X
-    return X
-
-
 def lib() -> C.CDLL:
-    return load(LIB_PATH, PREFIX)
+    """The count library with its calls typed; loaded once."""
+    return L.load(LIB_PATH, PREFIX, CALLS)
 
 
 def _device_u64(n: int, device: int):
@@ -63,9 +46,10 @@ def _device_u64(n: int, device: int):
     return torch.empty(max(n, 1), dtype=torch.int64, device=f"cuda:{device}")
 
 
-def upload_records(ctx: Context, records, pre: int):
+def _upload(ctx: Context, records, pre: int, with_offsets: bool):
     """Pack the records with the batch packer (ntk_batch_append: the pre-step's deleted bytes out, one break byte after each) and upload
-    them: (device tensor in the batch layout, n_bytes), or None for no records."""
+    them: (device tensor in the batch layout, n_bytes, the packer's record offsets as a device int64 tensor if asked for, n_records),
+    or None for no records."""
     import torch
     records = list(records)
     if not records:
@@ -75,22 +59,32 @@ def upload_records(ctx: Context, records, pre: int):
         for r in records:
             if not b.append(bytes(r), pre):
                 raise RuntimeError("batch sized for the records is full")
-        seq, _ = b.buffers()
+        seq, off = b.buffers()
         n = int(seq.size)
         dev = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=f"cuda:{ctx.device}")
         dev[:n] = torch.from_numpy(np.array(seq, copy=True)).to(dev.device)
+        d_off = torch.from_numpy(np.array(off, copy=True).view(np.int64)).to(dev.device) if with_offsets else None
         torch.cuda.synchronize(dev.device)
     finally:
         b.release()
-    return dev, n
+    return dev, n, d_off, len(records)
 
 
-class CountTable:
+def upload_records(ctx: Context, records, pre: int):
+    """The records packed and uploaded (_upload): (device batch, n_bytes), or None for no records."""
+    up = _upload(ctx, records, pre, False)
+    return up and up[:2]
+
+
+def upload_records_with_offsets(ctx: Context, records, pre: int):
+    """upload_records with the packer's record offsets: (device batch, n_bytes, device int64 offsets, n_records), or None."""
+    return _upload(ctx, records, pre, True)
+
+
+class CountTable(L.Handle):
     """What the count tables share: a table in device memory behind one library's eight calls.  A subclass names the library
-    (_lib_path, _prefix), the u64 words of a key (_key_words) and turns lookup's argument into queries (_queries)."""
+    (_lib, _prefix), the u64 words of a key (_key_words) and turns lookup's argument into queries (_queries)."""
 
-    _lib_path: str
-    _prefix: str
     _key_words: int
 
     def __init__(self, k: int, path: int, capacity: int, ctx: Context = None):
@@ -98,29 +92,6 @@ class CountTable:
         self.k, self.path = k, path
         self._h = C.c_void_p()
         self._check("create", self.ctx._h, k, path, capacity, C.byref(self._h))
-
-    def _fn(self, call: str):
-        return getattr(load(self._lib_path, self._prefix), self._prefix + call)
-
-    def _check(self, call: str, *args):
-        L.check(self._fn(call)(*args), self._prefix + call)
-
-    def close(self):
-        if self._h:
-            self._fn("destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def reset(self):
         self._check("reset", self._h)
@@ -191,7 +162,7 @@ class KmerTable(CountTable):
     returns keys as a uint64 array of values.  lookup() takes k-mers as bytes / str or packed values (canonicalised here for a
     canonical table); one k-mer given as bytes / str or an int reads an int."""
 
-    _lib_path, _prefix, _key_words = LIB_PATH, PREFIX, 1
+    _lib, _prefix, _key_words = staticmethod(lib), PREFIX, 1
 
     def _values(self, kmers) -> np.ndarray:
         if isinstance(kmers, (bytes, bytearray, str)):

@@ -12,14 +12,12 @@
 // counting pass per bit in which min and max differ - a handful for real spectra, never more than 64 - over counts the wave holds in
 // registers (up to kRegWindows windows) or re-reads through the caches.  DESIGN.md section 13.
 #include "../../include/needletail_amd_abundance.h"
-#define NTK_COUNT_COMMON_NO_TABLE   // the sums, the launch helpers and the scratch; no table
-#include "ntk_count_common.hpp"
+#include "ntk_consumer.hpp"
 
 #include <new>
 
 namespace {
 
-constexpr uint64_t kChunkBases = (uint64_t)64 << 20;     // bases materialised per pass (scratch: 10 B per base), as the count table
 constexpr int kWaveThreads = 256;                        // ra_wave_kernel: four records per block at a time
 constexpr int kBlockThreads = 1024;                      // ra_block_kernel: one long record per block at a time
 constexpr uint32_t kRegRounds = 3;                       // rounds of 64 windows a wave holds in registers
@@ -47,23 +45,6 @@ struct RaArgs {
     uint64_t long_cap;
     Row *rows;
 };
-
-__device__ inline uint64_t uniform(uint64_t v)   // a wave-uniform value, said so
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// the candidate window ends [lo, hi) of record r; an offset beyond the batch is read as its end
-__device__ inline void record_span(const RaArgs &a, uint64_t r, uint64_t &lo, uint64_t &hi)
-{
-    uint64_t b = a.offsets[r], e = a.offsets[r + 1];
-    if (e > a.n_bytes) e = a.n_bytes;
-    if (b > e) b = e;
-    hi = e ? e - 1 : 0;   // the last byte is the break byte
-    lo = b + a.k - 1;
-    if (lo > hi) lo = hi;
-}
 
 struct MinOp { __device__ uint64_t operator()(uint64_t x, uint64_t y) const { return x < y ? x : y; } };
 struct MaxOp { __device__ uint64_t operator()(uint64_t x, uint64_t y) const { return x > y ? x : y; } };
@@ -240,7 +221,7 @@ __global__ __launch_bounds__(kWaveThreads) void ra_wave_kernel(RaArgs a)
     const uint64_t first = (uint64_t)blockIdx.x * (kWaveThreads / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (uint64_t r = first; r < a.n_records; r += waves) {
         uint64_t lo, hi;
-        record_span(a, r, lo, hi);
+        record_span(a.offsets, a.n_bytes, a.k, r, lo, hi);
         const uint64_t span = hi - lo;
         if (span > kLongRecord) {
             if (lane == 0) {
@@ -263,7 +244,7 @@ __global__ __launch_bounds__(kBlockThreads) void ra_block_kernel(RaArgs a)
     for (uint64_t i = blockIdx.x; i < n_long; i += gridDim.x) {
         const uint64_t r = a.long_list[i];
         uint64_t lo, hi;
-        record_span(a, r, lo, hi);
+        record_span(a.offsets, a.n_bytes, a.k, r, lo, hi);
         const Row row = stream_row(a, lo, hi, BlockGroup{threadIdx.x, lds});
         if (threadIdx.x == 0) a.rows[r] = row;
     }
@@ -271,12 +252,8 @@ __global__ __launch_bounds__(kBlockThreads) void ra_block_kernel(RaArgs a)
 
 }  // namespace
 
-struct ntk_read_abundance {
-    ntk_ctx *ctx = nullptr;
+struct ntk_read_abundance : Consumer {   // k and path: the table's
     ntk_kmer_table *table = nullptr;   // borrowed
-    int device = 0, n_cu = 256;
-    hipStream_t stream = nullptr;
-    uint32_t k = 0, path = 0;          // the table's
     MaterialiseScratch scratch;        // of one chunk
     // batch-long, grown on demand
     uint64_t batch_bytes = 0;          // bases they hold (a multiple of 16)
@@ -319,17 +296,11 @@ int ntk_read_abundance_create(ntk_ctx *ctx, ntk_kmer_table *table, ntk_read_abun
     *out = nullptr;
     ntk_read_abundance *a = new (std::nothrow) ntk_read_abundance();
     if (!a) return NTK_ERR_NOMEM;
-    void *stream = nullptr;
-    int rc = ntk_ctx_stream(ctx, &a->device, &stream);
     struct ntk_kmer_table_stats st;
-    if (!rc) rc = ntk_kmer_table_stats(table, &st);
-    if (!rc) {
-        hipError_t e = hipSetDevice(a->device);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&a->n_cu, hipDeviceAttributeMultiprocessorCount, a->device);
-        if (e != hipSuccess) { (void)hipGetLastError(); rc = NTK_ERR_HIP; }
-    }
+    int rc = ntk_kmer_table_stats(table, &st);
+    if (!rc) rc = a->bind(ctx, st.k, st.path);
     if (rc) { delete a; return rc; }
-    a->ctx = ctx; a->table = table; a->stream = (hipStream_t)stream; a->k = st.k; a->path = st.path;
+    a->table = table;
     *out = a;
     return NTK_OK;
 }
@@ -356,34 +327,25 @@ int ntk_read_abundance_run_device(ntk_read_abundance *a, const uint8_t *d_seq, c
                                   const uint64_t *d_offsets, uint64_t n_records, const ntk_params *p, uint64_t min_count,
                                   struct ntk_read_abundance_row *d_rows)
 {
-    if (!a || !p) return NTK_ERR_BAD_ARG;
-    if (p->k != a->k || p->path != a->path || (p->flags & ~0xFF00u) != 0 || p->pre > NTK_PRE_NORMALIZE_IUPAC) return NTK_ERR_BAD_ARG;
-    if (p->path == NTK_PATH_BYTES_CANONICAL && p->pre < NTK_PRE_NORMALIZE) return NTK_ERR_UNSUPPORTED;
-    if (n_records == 0 || n_bytes == 0) return NTK_OK;
-    if (!d_seq || !d_offsets || !d_rows || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15) || ((uintptr_t)d_offsets & 7) ||
-        ((uintptr_t)d_rows & 7))
-        return NTK_ERR_BAD_ARG;
+    int rc = check_batch_params(a, p);
+    if (rc || n_records == 0 || n_bytes == 0) return rc;
+    if ((rc = check_batch_pointers(d_seq, d_qual))) return rc;
+    if (!d_offsets || !d_rows || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_rows & 7)) return NTK_ERR_BAD_ARG;
     CT_HIPCHK(hipSetDevice(a->device));
-    // chunks of kChunkBases, as the count table takes them: each chunk after the first is materialised from `halo` bytes before its
-    // start (a multiple of 16: d_seq stays aligned; >= k - 1: every window that ends in the chunk is whole).  Only the values and the
-    // plane words from the chunk's start on are taken, so the halo's partial windows never replace a good word of the chunk before.
-    const uint64_t halo = ((uint64_t)a->k - 1 + 15) & ~(uint64_t)15;
-    int rc = a->scratch.ensure(a->stream, (n_bytes < kChunkBases ? n_bytes : kChunkBases) + (n_bytes > kChunkBases ? halo : 0));
-    if (!rc) rc = a->ensure_batch(n_bytes);
-    if (rc) return rc;
-    for (uint64_t start = 0; start < n_bytes; start += kChunkBases) {
-        const uint64_t end = n_bytes - start > kChunkBases ? start + kChunkBases : n_bytes;
-        const uint64_t base = start ? start - halo : 0, len = end - base, skip = start - base;
-        rc = ntk_materialize_device_quality(a->ctx, d_seq + base, d_qual ? d_qual + base : nullptr, len, p, a->scratch.d_values,
-                                            a->scratch.d_valid16, a->scratch.d_rc16);
+    if ((rc = a->ensure_batch(n_bytes))) return rc;
+    // Of every chunk only the values and the plane words from its start on are taken, so the halo's partial windows never replace a good
+    // word of the chunk before.
+    rc = for_each_chunk(*a, a->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         // values at invalid positions are undefined: looking them up is a bounded read-only probe, and the plane drops their counts.
         // An incomplete table fails here, on the first chunk, before any row is written.  Synchronises.
-        if (!rc) rc = ntk_kmer_table_lookup_device(a->table, a->scratch.d_values + skip, end - start, a->d_counts + start);
+        const int rc = ntk_kmer_table_lookup_device(a->table, a->scratch.d_values + c.skip(), c.end - c.start, a->d_counts + c.start);
         if (rc) return rc;
         CT_HIPCHK(hipSetDevice(a->device));
-        CT_HIPCHK(hipMemcpyAsync(a->d_plane + start / 16, a->scratch.d_valid16 + skip / 16, (end - start + 15) / 16 * sizeof(uint16_t),
-                                 hipMemcpyDeviceToDevice, a->stream));
-    }
+        CT_HIPCHK(hipMemcpyAsync(a->d_plane + c.start / 16, a->scratch.d_valid16 + c.skip() / 16,
+                                 (c.end - c.start + 15) / 16 * sizeof(uint16_t), hipMemcpyDeviceToDevice, a->stream));
+        return NTK_OK;
+    });
+    if (rc) return rc;
     RaArgs g;
     g.counts = a->d_counts; g.plane = a->d_plane; g.offsets = d_offsets;
     g.n_bytes = n_bytes; g.n_records = n_records;

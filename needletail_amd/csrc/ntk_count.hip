@@ -4,7 +4,8 @@
 // Table: structure of arrays, keys[slots] (EMPTY = ~0) and counts[slots], 16 B per slot; slot = fmix64(key) & (slots - 1), then
 // linear probing, at most kProbeMax slots.  Keys are write-once (EMPTY -> key, claimed by an agent-scope CAS), counts change only
 // through agent-scope atomics.  The one key that equals EMPTY (NTK_PATH_BITS, k = 32, TTT...T) is counted in a side word.
-// DESIGN.md section 10 has the layout, the coherence argument and the chunking; ntk_count_common.hpp holds what the wide table shares.
+// DESIGN.md section 10 has the layout and the coherence argument, section 16 the chunking; ntk_count_common.hpp holds what the wide table
+// shares.
 #include "../../include/needletail_amd_count.h"
 #include "ntk_count_common.hpp"
 
@@ -13,7 +14,6 @@
 
 namespace {
 
-constexpr uint64_t kChunkBases = (uint64_t)64 << 20;     // bases materialised per pass (scratch: 10 B per base)
 // stats words on the device: the shared ones, then the side word of the all-ones key
 constexpr int kStOnes = 3, kStWords = 4;
 
@@ -158,34 +158,22 @@ int ntk_kmer_table_reset(ntk_kmer_table *t)
 
 int ntk_kmer_table_count_device(ntk_kmer_table *t, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes, const ntk_params *p)
 {
-    if (!t || !p) return NTK_ERR_BAD_ARG;
-    if (p->k != t->k || p->path != t->path || (p->flags & ~0xFF00u) != 0 || p->pre > NTK_PRE_NORMALIZE_IUPAC) return NTK_ERR_BAD_ARG;
-    if (p->path == NTK_PATH_BYTES_CANONICAL && p->pre < NTK_PRE_NORMALIZE) return NTK_ERR_UNSUPPORTED;
-    if (n_bytes == 0) return NTK_OK;
-    if (!d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15)) return NTK_ERR_BAD_ARG;
+    int rc = check_batch_params(t, p);
+    if (rc || n_bytes == 0) return rc;
+    if ((rc = check_batch_pointers(d_seq, d_qual))) return rc;
     CT_HIPCHK(hipSetDevice(t->device));
-    // chunks of kChunkBases; each chunk after the first is materialised from `halo` bytes before its start (a multiple of 16: d_seq
-    // stays aligned; >= k - 1: every window that ends in the chunk is whole), and only windows ending at or after the start count
-    const uint64_t halo = ((uint64_t)t->k - 1 + 15) & ~(uint64_t)15;
-    int rc = t->scratch.ensure(t->stream, (n_bytes < kChunkBases ? n_bytes : kChunkBases) + (n_bytes > kChunkBases ? halo : 0));
-    if (rc) return rc;
-    for (uint64_t start = 0; start < n_bytes; start += kChunkBases) {
-        const uint64_t end = n_bytes - start > kChunkBases ? start + kChunkBases : n_bytes;
-        const uint64_t base = start ? start - halo : 0, len = end - base;
-        rc = ntk_materialize_device_quality(t->ctx, d_seq + base, d_qual ? d_qual + base : nullptr, len, p, t->scratch.d_values,
-                                            t->scratch.d_valid16, t->scratch.d_rc16);
-        if (rc) return rc;
-        CT_HIPCHK(hipSetDevice(t->device));
+    // of every chunk only the windows ending at or after its start count
+    return for_each_chunk(*t, t->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         InsertArgs a;
         a.values = t->scratch.d_values; a.valid16 = t->scratch.d_valid16;
-        a.first = start - base; a.n = len;
+        a.first = c.skip(); a.n = c.len();
         a.keys = t->d_keys; a.counts = t->d_counts; a.stats = t->d_stats;
         a.mask = t->slots - 1; a.probe_max = t->probe_max;
-        hipLaunchKernelGGL(kt_insert_kernel, dim3(grid_for(len - a.first, kThreads, (unsigned)t->n_cu * 8)), dim3(kThreads), 0,
+        hipLaunchKernelGGL(kt_insert_kernel, dim3(grid_for(a.n - a.first, kThreads, (unsigned)t->n_cu * 8)), dim3(kThreads), 0,
                            t->stream, a);
         CT_HIPCHK(hipGetLastError());
-    }
-    return NTK_OK;
+        return NTK_OK;
+    });
 }
 
 int ntk_kmer_table_stats(ntk_kmer_table *t, struct ntk_kmer_table_stats *out)

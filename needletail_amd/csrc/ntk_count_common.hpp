@@ -1,69 +1,25 @@
-// What the two count tables share (ntk_count.hip: k <= 32, one key word; ntk_wide_count.hip: k = 33..63, two key words): the
-// constants, the hash, the wave and block sums, the extract count / scan and spectrum kernels, and TableCore, the host side of a table
-// apart from its key words, and the scratch of the materialise face, which the sketch (ntk_sketch.hip) takes from here as well, with
-// the hash and the sums (it defines NTK_COUNT_COMMON_NO_TABLE first: no table kernel, no TableCore, so its library ships none of
-// them).  The read-side kernels see a table as its occupancy words (`occ`: the narrow keys, the wide hi; EMPTY =
-// free) and its counts.  Everything is in an anonymous namespace, so each library keeps a private copy and exports nothing new.
-// DESIGN.md sections 10 and 11.
+// What the two count tables share (ntk_count.hip: k <= 32, one key word; ntk_wide_count.hip: k = 33..63, two key words) on top of what
+// every consumer of the core's ABI does (ntk_consumer.hpp): the constants, the extract count / scan and spectrum kernels, and TableCore,
+// the host side of a table apart from its key words.  The read-side kernels see a table as its occupancy words (`occ`: the narrow
+// keys, the wide hi; EMPTY = free) and its counts.  Everything is in an anonymous namespace, so each library keeps a private copy and
+// exports nothing new.  DESIGN.md sections 10 and 11.
 #pragma once
 
-#include "../../include/needletail_amd.h"
-
-#include <hip/hip_runtime.h>
+#include "ntk_consumer.hpp"
 
 #include <cstring>
 #include <initializer_list>
-
-#define CT_HIPCHK(expr)                      \
-    do {                                     \
-        hipError_t e__ = (expr);             \
-        if (e__ != hipSuccess) {             \
-            (void)hipGetLastError();         \
-            return NTK_ERR_HIP;              \
-        }                                    \
-    } while (0)
 
 namespace {
 
 constexpr uint64_t kEmpty = ~(uint64_t)0;
 constexpr uint32_t kProbeMax = 4096;                     // probe bound: a full or adversarial table never makes a kernel run long
-constexpr int kThreads = 256;
 constexpr uint32_t kExtractPerThread = 32;               // slots per thread of the extract count / scatter kernels
 constexpr uint64_t kExtractPerBlock = (uint64_t)kThreads * kExtractPerThread;
 constexpr uint32_t kMaxBins = 16384;
 // stats words on the device that both tables keep
 constexpr int kStDistinct = 0, kStTotal = 1, kStDropped = 2;
 
-__host__ __device__ inline uint64_t fmix64(uint64_t x)
-{
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
-
-__device__ inline uint64_t wave_sum(uint64_t v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ inline void add_agent(uint64_t *p, uint64_t v)
-{
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ inline uint32_t block_sum_u32(uint32_t v, uint32_t *lds)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t s = 0;
-    for (int w = 0; w < kThreads / 64; w++) s += lds[w];
-    return s;
-}
-
-#ifndef NTK_COUNT_COMMON_NO_TABLE
 // extract, step 1: occupied slots with count >= min_count, per block of kExtractPerBlock slots
 __global__ __launch_bounds__(kThreads) void ct_extract_count_kernel(const uint64_t *occ, const uint64_t *counts, uint64_t slots,
                                                                     uint64_t min_count, uint32_t *block_counts)
@@ -117,61 +73,10 @@ __global__ __launch_bounds__(kThreads) void ct_spectrum_kernel(const uint64_t *o
         if (bins[b]) add_agent(hist + b, bins[b]);
 }
 
-#endif  // NTK_COUNT_COMMON_NO_TABLE
-
-inline unsigned grid_for(uint64_t items, unsigned block, unsigned cap)
-{
-    const uint64_t b = (items + block - 1) / block;
-    return (unsigned)(b > cap ? cap : (b ? b : 1));
-}
-
-int alloc_status(hipError_t e)
-{
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? NTK_ERR_NOMEM : NTK_ERR_HIP;
-}
-
-// The scratch of one chunk of the core's materialise face (values, valid plane, strand plane: 10 B per base), grown on demand.  Owned by
-// whatever consumes that face chunk by chunk: the narrow table and the sketch (ntk_sketch.hip).
-struct MaterialiseScratch {
-    uint64_t bytes = 0;   // bases it holds (a multiple of 16)
-    uint64_t *d_values = nullptr;
-    uint16_t *d_valid16 = nullptr, *d_rc16 = nullptr;
-
-    void release()
-    {
-        if (d_values) (void)hipFree(d_values);
-        if (d_valid16) (void)hipFree(d_valid16);
-        if (d_rc16) (void)hipFree(d_rc16);
-        d_values = nullptr; d_valid16 = d_rc16 = nullptr; bytes = 0;
-    }
-
-    int ensure(hipStream_t stream, uint64_t len)
-    {
-        const uint64_t need = (len + 15) & ~(uint64_t)15;
-        if (need <= bytes) return NTK_OK;
-        CT_HIPCHK(hipStreamSynchronize(stream));   // the old scratch may still be read by queued kernels
-        release();
-        hipError_t e;
-        if ((e = hipMalloc((void **)&d_values, need * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_valid16, need / 16 * sizeof(uint16_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_rc16, need / 16 * sizeof(uint16_t))) != hipSuccess) {
-            release();
-            return alloc_status(e);
-        }
-        bytes = need;
-        return NTK_OK;
-    }
-};
-
-#ifndef NTK_COUNT_COMMON_NO_TABLE
 // The host side of a table apart from its key words, which the table adds (keys; hi, lo) and hands to the helpers that set up, clear
 // or free every slot array.  `stat_words`: the length of the table's stats array.
-struct TableCore {
-    ntk_ctx *ctx = nullptr;
-    int device = 0, n_cu = 256;
-    hipStream_t stream = nullptr;
-    uint32_t k = 0, path = 0, probe_max = kProbeMax;
+struct TableCore : Consumer {
+    uint32_t probe_max = kProbeMax;
     uint64_t slots = 0;
     uint64_t *d_counts = nullptr;
     uint64_t *d_stats = nullptr, *d_hist = nullptr, *d_offsets = nullptr;
@@ -183,17 +88,10 @@ struct TableCore {
     // the context's device and stream, the table's size and probe bound; no allocation yet
     int init(ntk_ctx *c, uint32_t k_, uint32_t path_, uint64_t capacity)
     {
-        void *s = nullptr;
-        int rc = ntk_ctx_stream(c, &device, &s);
-        if (rc) return rc;
-        ctx = c; stream = (hipStream_t)s; k = k_; path = path_;
         slots = 2;
         while (capacity * 4 > slots * 3) slots <<= 1;   // capacity <= 0.75 * slots
         probe_max = slots < kProbeMax ? (uint32_t)slots : kProbeMax;
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
-        if (e != hipSuccess) { (void)hipGetLastError(); return NTK_ERR_HIP; }
-        return NTK_OK;
+        return bind(c, k_, path_);
     }
 
     // the key words (one u64 per slot each), then the counts and the buffers of stats, extract and spectrum
@@ -312,6 +210,5 @@ struct TableCore {
         return NTK_OK;
     }
 };
-#endif  // NTK_COUNT_COMMON_NO_TABLE
 
 }  // namespace

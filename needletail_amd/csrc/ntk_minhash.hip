@@ -2,7 +2,7 @@
 // core's public ABI like the cardinality sketch (ntk_sketch.hip), with its two routes: k <= 32 reads the values
 // ntk_materialize_device_quality emits, k = 33..63 walks the batch bytes (ntk_wide_walk.hpp).
 //
-// THE ONE PLACE that fixes the hash is minhash_hash below (fmix64 is ntk_count_common.hpp's, the tables' hash): the sketch library's
+// THE ONE PLACE that fixes the hash is minhash_hash below (fmix64 is ntk_consumer.hpp's, the tables' hash): the sketch library's
 // hash, restated; the header states it and tests/_minhash_model.py takes it from tests/_sketch_model.py.
 //
 // State: S, the kept (hash, count) pairs, sorted and unique; the threshold tau, the largest hash that can still enter (it only falls);
@@ -13,8 +13,7 @@
 // <= the final tau has every one of its occurrences in S or the buffer.  Adds on the one counter serialise (about 12 ns each), so an
 // optimistic launch reserves per wave and kSlab slots at a time and pads what a wave leaves unused.  DESIGN.md section 15.
 #include "../../include/needletail_amd_minhash.h"
-#define NTK_COUNT_COMMON_NO_TABLE   // the hash, the sums, the launch helpers and the scratch; no table
-#include "ntk_count_common.hpp"
+#include "ntk_consumer.hpp"
 #include "ntk_wide_walk.hpp"
 
 #include <rocprim/device/device_merge.hpp>
@@ -28,7 +27,6 @@
 namespace {
 
 constexpr uint64_t kXor = 0x9E3779B97F4A7C15ull;         // C: key 0 (AAA...A) must not hash to 0
-constexpr uint64_t kChunkBases = (uint64_t)64 << 20;     // bases materialised per pass (scratch: 10 B per base), as the count table
 constexpr int kFilterThreads = 256;                      // 64 B of LDS, few registers: eight blocks per CU keep 8 waves per SIMD
 constexpr unsigned kBlocksPerCu = 8;
 constexpr uint32_t kPerLane = 4;                         // window ends per lane and round of mh_filter_kernel (loads in flight)
@@ -232,11 +230,7 @@ struct Pairs {
 
 }  // namespace
 
-struct ntk_minhash {
-    ntk_ctx *ctx = nullptr;
-    int device = 0, n_cu = 256;
-    hipStream_t stream = nullptr;
-    uint32_t k = 0, path = 0;
+struct ntk_minhash : Consumer {
     uint64_t num = 0, scaled = 0, max_hash = kAll;
     uint64_t cap = 0;                 // buffer_entries
     uint64_t *d_buf = nullptr;        // the candidate buffer
@@ -487,15 +481,11 @@ int ntk_minhash_create(ntk_ctx *ctx, uint32_t k, uint32_t path, uint64_t num, ui
     if (buffer_entries < NTK_MINHASH_BUFFER_MIN || buffer_entries > NTK_MINHASH_BUFFER_MAX) return NTK_ERR_BAD_ARG;
     ntk_minhash *m = new (std::nothrow) ntk_minhash();
     if (!m) return NTK_ERR_NOMEM;
-    void *stream = nullptr;
-    int rc = ntk_ctx_stream(ctx, &m->device, &stream);
+    int rc = m->bind(ctx, k, path);
     if (rc) { delete m; return rc; }
-    m->ctx = ctx; m->stream = (hipStream_t)stream; m->k = k; m->path = path;
     m->num = num; m->scaled = scaled; m->max_hash = scaled ? kAll / scaled : kAll;
     m->cap = buffer_entries;
-    hipError_t e = hipSetDevice(m->device);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&m->n_cu, hipDeviceAttributeMultiprocessorCount, m->device);
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_buf, m->cap * sizeof(uint64_t));
+    hipError_t e = hipMalloc((void **)&m->d_buf, m->cap * sizeof(uint64_t));
     if (e == hipSuccess) e = hipMalloc((void **)&m->d_sorted, m->cap * sizeof(uint64_t));
     if (e == hipSuccess) e = hipMalloc((void **)&m->d_ctr, 4 * sizeof(uint64_t));
     if (e == hipSuccess) e = hipHostMalloc((void **)&m->h_stage, 4 * sizeof(uint64_t), hipHostMallocDefault);
@@ -532,11 +522,9 @@ int ntk_minhash_reset(ntk_minhash *m)
 
 int ntk_minhash_add_device(ntk_minhash *m, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes, const ntk_params *p)
 {
-    if (!m || !p) return NTK_ERR_BAD_ARG;
-    if (p->k != m->k || p->path != m->path || (p->flags & ~0xFF00u) != 0 || p->pre > NTK_PRE_NORMALIZE_IUPAC) return NTK_ERR_BAD_ARG;
-    if (p->path == NTK_PATH_BYTES_CANONICAL && p->pre < NTK_PRE_NORMALIZE) return NTK_ERR_UNSUPPORTED;
-    if (n_bytes == 0) return NTK_OK;
-    if (!d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15)) return NTK_ERR_BAD_ARG;
+    int rc = check_batch_params(m, p);
+    if (rc || n_bytes == 0) return rc;
+    if ((rc = check_batch_pointers(d_seq, d_qual))) return rc;
     if (m->failed) return m->failed;
     return settled(m, [&]() -> int {
     CT_HIPCHK(hipSetDevice(m->device));
@@ -553,29 +541,16 @@ int ntk_minhash_add_device(ntk_minhash *m, const uint8_t *d_seq, const uint8_t *
             hipLaunchKernelGGL(mh_wide_filter_kernel, dim3(grid_for(hi - lo, kFilterThreads, resident)), dim3(kFilterThreads), 0, m->stream, a);
         });
     }
-    // chunks of kChunkBases, as the count table takes them: each chunk after the first is materialised from `halo` bytes before its
-    // start (a multiple of 16: d_seq stays aligned; >= k - 1: every window that ends in the chunk is whole), and only windows ending
-    // at or after the start are taken
-    const uint64_t halo = ((uint64_t)m->k - 1 + 15) & ~(uint64_t)15;
-    int rc = m->scratch.ensure(m->stream, (n_bytes < kChunkBases ? n_bytes : kChunkBases) + (n_bytes > kChunkBases ? halo : 0));
-    if (rc) return rc;
-    for (uint64_t start = 0; start < n_bytes; start += kChunkBases) {
-        const uint64_t end = n_bytes - start > kChunkBases ? start + kChunkBases : n_bytes;
-        const uint64_t base = start ? start - halo : 0, len = end - base;
-        rc = ntk_materialize_device_quality(m->ctx, d_seq + base, d_qual ? d_qual + base : nullptr, len, p, m->scratch.d_values,
-                                            m->scratch.d_valid16, m->scratch.d_rc16);
-        if (rc) return rc;
-        CT_HIPCHK(hipSetDevice(m->device));
+    // of every chunk only the windows ending at or after its start are taken
+    return for_each_chunk(*m, m->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         FilterArgs a;
         a.values = m->scratch.d_values; a.valid16 = m->scratch.d_valid16;
-        rc = run_range(m, start - base, len, 1, [&](uint64_t lo, uint64_t hi, uint32_t slabs) {
+        return run_range(m, c.skip(), c.len(), 1, [&](uint64_t lo, uint64_t hi, uint32_t slabs) {
             a.first = lo; a.n = hi; a.c = candidates(m, slabs);
             const uint64_t rounds = (hi - lo + kPerLane - 1) / kPerLane;
             hipLaunchKernelGGL(mh_filter_kernel, dim3(grid_for(rounds, kFilterThreads, resident)), dim3(kFilterThreads), 0, m->stream, a);
         });
-        if (rc) return rc;
-    }
-    return NTK_OK;
+    });
     }());
 }
 

@@ -3,7 +3,7 @@
 // ntk_materialize_device_quality emits (every path's keys are the core's by construction), k = 33..63 walks the batch bytes as the
 // wide table's count kernel does (walk_lane_run below).
 //
-// THE ONE PLACE that fixes hash, index and rank is sketch_slot / sketch_rank below (fmix64 is ntk_count_common.hpp's, the tables'
+// THE ONE PLACE that fixes hash, index and rank is sketch_slot / sketch_rank below (fmix64 is ntk_consumer.hpp's, the tables'
 // hash); the header states them and tests/_sketch_model.py restates them.
 //
 // Update scheme: after the first few hundred thousand keys almost no key raises a register (a register holds about log2(n / m)), so
@@ -13,10 +13,10 @@
 // wrong result.  The grid is two blocks per CU with a grid-stride loop: the flush is paid per resident block, not per unit of work.
 // DESIGN.md section 12.
 #include "../../include/needletail_amd_sketch.h"
-#define NTK_COUNT_COMMON_NO_TABLE   // the hash, the sums, the launch helpers and the scratch; no table
-#include "ntk_count_common.hpp"
+#include "ntk_consumer.hpp"
 
 #include <cmath>
+#include <cstring>
 #include <new>
 
 namespace {
@@ -24,7 +24,6 @@ namespace {
 constexpr uint32_t kP = NTK_SKETCH_P, kRegisters = NTK_SKETCH_REGISTERS;
 constexpr uint32_t kRankMax = 64 - kP + 1;               // 51: every one of the 50 bits below the index is zero
 constexpr uint64_t kXor = 0x9E3779B97F4A7C15ull;         // C: key 0 (AAA...A) must not hash to 0
-constexpr uint64_t kChunkBases = (uint64_t)64 << 20;     // bases materialised per pass (scratch: 10 B per base), as the count table
 constexpr int kSketchThreads = 1024;                     // 16 waves per block: two blocks (2 x 64 KiB of LDS) keep 8 waves per SIMD
 constexpr uint32_t kPerLane = 4;                         // window ends per lane and round of sk_update_kernel (loads in flight)
 constexpr uint32_t kKMax = 63;
@@ -197,11 +196,7 @@ void evaluate(const uint64_t *c, uint64_t n_windows, uint32_t k, struct ntk_kmer
 
 }  // namespace
 
-struct ntk_kmer_sketch {
-    ntk_ctx *ctx = nullptr;
-    int device = 0, n_cu = 256;
-    hipStream_t stream = nullptr;
-    uint32_t k = 0, path = 0;
+struct ntk_kmer_sketch : Consumer {
     uint32_t *d_regs = nullptr;       // the registers as the kernels keep them: one 32-bit word each
     uint64_t *d_windows = nullptr;    // k-mers added by add_device since reset
     uint64_t merged_windows = 0;      // k-mers of the sketches merged in since reset
@@ -235,13 +230,9 @@ int ntk_kmer_sketch_create(ntk_ctx *ctx, uint32_t k, uint32_t path, ntk_kmer_ske
     if (k > 32 && path != NTK_PATH_BYTES_CANONICAL) return NTK_ERR_BAD_K;   // the 2-bit iterator stops at k = 32
     ntk_kmer_sketch *s = new (std::nothrow) ntk_kmer_sketch();
     if (!s) return NTK_ERR_NOMEM;
-    void *stream = nullptr;
-    int rc = ntk_ctx_stream(ctx, &s->device, &stream);
+    int rc = s->bind(ctx, k, path);
     if (rc) { delete s; return rc; }
-    s->ctx = ctx; s->stream = (hipStream_t)stream; s->k = k; s->path = path;
-    hipError_t e = hipSetDevice(s->device);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&s->n_cu, hipDeviceAttributeMultiprocessorCount, s->device);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_regs, kRegisters * sizeof(uint32_t));
+    hipError_t e = hipMalloc((void **)&s->d_regs, kRegisters * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&s->d_windows, sizeof(uint64_t));
     if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_stage, (kRegisters + 2) * sizeof(uint32_t), hipHostMallocDefault);
     rc = e == hipSuccess ? ntk_kmer_sketch_reset(s) : alloc_status(e);
@@ -275,11 +266,9 @@ int ntk_kmer_sketch_reset(ntk_kmer_sketch *s)
 
 int ntk_kmer_sketch_add_device(ntk_kmer_sketch *s, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes, const ntk_params *p)
 {
-    if (!s || !p) return NTK_ERR_BAD_ARG;
-    if (p->k != s->k || p->path != s->path || (p->flags & ~0xFF00u) != 0 || p->pre > NTK_PRE_NORMALIZE_IUPAC) return NTK_ERR_BAD_ARG;
-    if (p->path == NTK_PATH_BYTES_CANONICAL && p->pre < NTK_PRE_NORMALIZE) return NTK_ERR_UNSUPPORTED;
-    if (n_bytes == 0) return NTK_OK;
-    if (!d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15)) return NTK_ERR_BAD_ARG;
+    int rc = check_batch_params(s, p);
+    if (rc || n_bytes == 0) return rc;
+    if ((rc = check_batch_pointers(d_seq, d_qual))) return rc;
     CT_HIPCHK(hipSetDevice(s->device));
     const unsigned resident = (unsigned)s->n_cu * 2;
     if (s->k > 32) {
@@ -294,28 +283,17 @@ int ntk_kmer_sketch_add_device(ntk_kmer_sketch *s, const uint8_t *d_seq, const u
         CT_HIPCHK(hipGetLastError());
         return NTK_OK;
     }
-    // chunks of kChunkBases, as the count table takes them: each chunk after the first is materialised from `halo` bytes before its
-    // start (a multiple of 16: d_seq stays aligned; >= k - 1: every window that ends in the chunk is whole), and only windows ending
-    // at or after the start are taken - the max would not mind a window twice, n_windows does
-    const uint64_t halo = ((uint64_t)s->k - 1 + 15) & ~(uint64_t)15;
-    int rc = s->scratch.ensure(s->stream, (n_bytes < kChunkBases ? n_bytes : kChunkBases) + (n_bytes > kChunkBases ? halo : 0));
-    if (rc) return rc;
-    for (uint64_t start = 0; start < n_bytes; start += kChunkBases) {
-        const uint64_t end = n_bytes - start > kChunkBases ? start + kChunkBases : n_bytes;
-        const uint64_t base = start ? start - halo : 0, len = end - base;
-        rc = ntk_materialize_device_quality(s->ctx, d_seq + base, d_qual ? d_qual + base : nullptr, len, p, s->scratch.d_values,
-                                            s->scratch.d_valid16, s->scratch.d_rc16);
-        if (rc) return rc;
-        CT_HIPCHK(hipSetDevice(s->device));
+    // of every chunk only the windows ending at or after its start are taken - the max would not mind a window twice, n_windows does
+    return for_each_chunk(*s, s->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         UpdateArgs a;
         a.values = s->scratch.d_values; a.valid16 = s->scratch.d_valid16;
-        a.first = start - base; a.n = len;
+        a.first = c.skip(); a.n = c.len();
         a.regs = s->d_regs; a.n_windows = s->d_windows;
-        const uint64_t rounds = (len - a.first + kPerLane - 1) / kPerLane;
+        const uint64_t rounds = (a.n - a.first + kPerLane - 1) / kPerLane;
         hipLaunchKernelGGL(sk_update_kernel, dim3(grid_for(rounds, kSketchThreads, resident)), dim3(kSketchThreads), 0, s->stream, a);
         CT_HIPCHK(hipGetLastError());
-    }
-    return NTK_OK;
+        return NTK_OK;
+    });
 }
 
 int ntk_kmer_sketch_registers(ntk_kmer_sketch *s, uint8_t *regs)

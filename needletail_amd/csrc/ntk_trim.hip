@@ -1,6 +1,6 @@
 // Trimming reads by k-mer abundance and writing the kept reads out as a batch (include/needletail_amd_trim.h).  A consumer of the
-// public ABIs like the abundance library: per 64 MiB chunk (with the round_up(k - 1, 16) halo of the count table, taking only what ends
-// at or after the chunk's start) the k-mers are the values ntk_materialize_device_quality emits and their counts are
+// public ABIs like the abundance library: per chunk of the batch (for_each_chunk of ntk_consumer.hpp, taking only what ends at or after
+// the chunk's start) the k-mers are the values ntk_materialize_device_quality emits and their counts are
 // ntk_kmer_table_lookup_device's, into a CHUNK-long count array.  This file's own device code:
 //
 //   rt_solid_kernel     one lane per window end of the chunk: ballot(valid && count >= min_count) is one 64-bit word of the batch-long
@@ -15,8 +15,7 @@
 //
 // Plane layout: bit e % 64 of word e / 64 is the window that ends at batch byte e.  DESIGN.md section 14.
 #include "../../include/needletail_amd_trim.h"
-#define NTK_COUNT_COMMON_NO_TABLE   // the launch helpers and the scratch; no table
-#include "ntk_count_common.hpp"
+#include "ntk_consumer.hpp"
 #include "ntk_trim_runs.hpp"
 
 #include <new>
@@ -26,7 +25,6 @@
 
 namespace {
 
-constexpr uint64_t kChunkBases = (uint64_t)64 << 20;     // bases materialised and looked up per pass, as the count table
 constexpr int kSolidThreads = 256;                       // rt_solid_kernel: a wave takes kSolidRounds * 64 window ends at a time
 constexpr uint32_t kSolidRounds = 4;                     // 8-byte count loads a lane has in flight
 constexpr int kIntervalThreads = 256;
@@ -38,12 +36,6 @@ constexpr uint64_t kLongPieces = 2048;                   // a record of more 16-
 
 using Row = ntk_read_trim_row;
 static_assert(sizeof(Row) == 32, "the header states the row");
-
-__device__ inline uint64_t uniform(uint64_t v)   // a wave-uniform value, said so
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
-}
 
 // ---- the solid and valid planes of one chunk -------------------------------------------------------------------------------------------
 
@@ -99,17 +91,6 @@ struct IntervalArgs {
     uint32_t k, prefix;
     Row *rows;
 };
-
-// the candidate window ends [lo, hi) of record r; an offset beyond the batch is read as its end (ntk_abundance.hip's rule)
-__device__ inline void record_span(const uint64_t *offsets, uint64_t n_bytes, uint32_t k, uint64_t r, uint64_t &lo, uint64_t &hi)
-{
-    uint64_t b = offsets[r], e = offsets[r + 1];
-    if (e > n_bytes) e = n_bytes;
-    if (b > e) b = e;
-    hi = e ? e - 1 : 0;   // the last byte is the break byte
-    lo = b + k - 1;
-    if (lo > hi) lo = hi;
-}
 
 template <uint32_t G>
 __device__ inline RtRuns shuffle_down(const RtRuns &v, uint32_t off)
@@ -351,12 +332,8 @@ __global__ __launch_bounds__(kCopyThreads) void rt_copy_long_kernel(CopyArgs a)
 
 }  // namespace
 
-struct ntk_read_trim {
-    ntk_ctx *ctx = nullptr;
+struct ntk_read_trim : Consumer {        // k and path: the table's
     ntk_kmer_table *table = nullptr;   // borrowed
-    int device = 0, n_cu = 256;
-    hipStream_t stream = nullptr;
-    uint32_t k = 0, path = 0;          // the table's
     MaterialiseScratch scratch;        // of one chunk
     uint64_t chunk_bases = 0;          // bases d_counts holds (a multiple of 16, at most kChunkBases)
     uint64_t *d_counts = nullptr;      // 8 B per base of one chunk
@@ -422,17 +399,11 @@ int ntk_read_trim_create(ntk_ctx *ctx, ntk_kmer_table *table, ntk_read_trim **ou
     *out = nullptr;
     ntk_read_trim *t = new (std::nothrow) ntk_read_trim();
     if (!t) return NTK_ERR_NOMEM;
-    void *stream = nullptr;
-    int rc = ntk_ctx_stream(ctx, &t->device, &stream);
     struct ntk_kmer_table_stats st;
-    if (!rc) rc = ntk_kmer_table_stats(table, &st);
-    if (!rc) {
-        hipError_t e = hipSetDevice(t->device);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&t->n_cu, hipDeviceAttributeMultiprocessorCount, t->device);
-        if (e != hipSuccess) { (void)hipGetLastError(); rc = NTK_ERR_HIP; }
-    }
+    int rc = ntk_kmer_table_stats(table, &st);
+    if (!rc) rc = t->bind(ctx, st.k, st.path);
     if (rc) { delete t; return rc; }
-    t->ctx = ctx; t->table = table; t->stream = (hipStream_t)stream; t->k = st.k; t->path = st.path;
+    t->table = table;
     *out = t;
     return NTK_OK;
 }
@@ -458,41 +429,32 @@ int ntk_read_trim_run_device(ntk_read_trim *t, const uint8_t *d_seq, const uint8
                              const uint64_t *d_offsets, uint64_t n_records, const ntk_params *p, uint64_t min_count, uint32_t mode,
                              uint64_t min_length, struct ntk_read_trim_row *d_rows)
 {
-    if (!t || !p) return NTK_ERR_BAD_ARG;
-    if (p->k != t->k || p->path != t->path || (p->flags & ~0xFF00u) != 0 || p->pre > NTK_PRE_NORMALIZE_IUPAC) return NTK_ERR_BAD_ARG;
     if (mode != NTK_TRIM_PREFIX && mode != NTK_TRIM_LONGEST) return NTK_ERR_BAD_ARG;
-    if (p->path == NTK_PATH_BYTES_CANONICAL && p->pre < NTK_PRE_NORMALIZE) return NTK_ERR_UNSUPPORTED;
-    if (n_records == 0 || n_bytes == 0) return NTK_OK;
-    if (!d_seq || !d_offsets || !d_rows || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15) || ((uintptr_t)d_offsets & 7) ||
-        ((uintptr_t)d_rows & 7))
-        return NTK_ERR_BAD_ARG;
+    int rc = check_batch_params(t, p);
+    if (rc || n_records == 0 || n_bytes == 0) return rc;
+    if ((rc = check_batch_pointers(d_seq, d_qual))) return rc;
+    if (!d_offsets || !d_rows || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_rows & 7)) return NTK_ERR_BAD_ARG;
     CT_HIPCHK(hipSetDevice(t->device));
-    // chunks of kChunkBases with a halo, as ntk_read_abundance_run_device takes them; the counts of a chunk are turned into plane
-    // words before the next chunk's replace them
-    const uint64_t halo = ((uint64_t)t->k - 1 + 15) & ~(uint64_t)15;
-    const uint64_t chunk = n_bytes < kChunkBases ? n_bytes : kChunkBases;
-    int rc = t->scratch.ensure(t->stream, chunk + (n_bytes > kChunkBases ? halo : 0));
-    if (!rc) rc = t->grow(t->d_counts, t->chunk_bases, (chunk + 15) & ~(uint64_t)15, sizeof(uint64_t));
+    rc = t->grow(t->d_counts, t->chunk_bases, (chunk_bases(n_bytes) + 15) & ~(uint64_t)15, sizeof(uint64_t));
     if (!rc) rc = ensure_planes(t, n_bytes);
     if (rc) return rc;
-    for (uint64_t start = 0; start < n_bytes; start += kChunkBases) {
-        const uint64_t end = n_bytes - start > kChunkBases ? start + kChunkBases : n_bytes;
-        const uint64_t base = start ? start - halo : 0, len = end - base, skip = start - base;
-        rc = ntk_materialize_device_quality(t->ctx, d_seq + base, d_qual ? d_qual + base : nullptr, len, p, t->scratch.d_values,
-                                            t->scratch.d_valid16, t->scratch.d_rc16);
+    // the counts of a chunk are turned into plane words before the next chunk's replace them
+    rc = for_each_chunk(*t, t->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         // values at invalid positions are undefined: looking them up is a bounded read-only probe, and the valid bit drops their counts.
         // An incomplete table fails here, on the first chunk, before any row is written.  Synchronises.
-        if (!rc) rc = ntk_kmer_table_lookup_device(t->table, t->scratch.d_values + skip, end - start, t->d_counts);
+        const int rc = ntk_kmer_table_lookup_device(t->table, t->scratch.d_values + c.skip(), c.end - c.start, t->d_counts);
         if (rc) return rc;
         CT_HIPCHK(hipSetDevice(t->device));
         SolidArgs g;
-        g.counts = t->d_counts; g.valid16 = t->scratch.d_valid16 + skip / 16;
-        g.n = end - start; g.min_count = min_count ? min_count : 1;
-        g.solid = t->d_solid + start / 64; g.valid = t->d_valid + start / 64;
+        g.counts = t->d_counts; g.valid16 = t->scratch.d_valid16 + c.skip() / 16;
+        g.n = c.end - c.start; g.min_count = min_count ? min_count : 1;
+        g.solid = t->d_solid + c.start / 64; g.valid = t->d_valid + c.start / 64;
         hipLaunchKernelGGL(rt_solid_kernel, dim3(grid_for(g.n, 64 * kSolidRounds * (kSolidThreads / 64), (unsigned)t->n_cu * 8)),
                            dim3(kSolidThreads), 0, t->stream, g);
         CT_HIPCHK(hipGetLastError());
-    }
+        return NTK_OK;
+    });
+    if (rc) return rc;
     IntervalArgs g;
     g.solid = t->d_solid; g.valid = t->d_valid; g.offsets = d_offsets;
     g.n_bytes = n_bytes; g.n_records = n_records; g.min_length = min_length;

@@ -242,11 +242,9 @@ int ntk_wide_table_reset(ntk_wide_table *t)
 
 int ntk_wide_table_count_device(ntk_wide_table *t, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes, const ntk_params *p)
 {
-    if (!t || !p) return NTK_ERR_BAD_ARG;
-    if (p->k != t->k || p->path != t->path || (p->flags & ~0xFF00u) != 0 || p->pre > NTK_PRE_NORMALIZE_IUPAC) return NTK_ERR_BAD_ARG;
-    if (p->pre < NTK_PRE_NORMALIZE) return NTK_ERR_UNSUPPORTED;
-    if (n_bytes == 0) return NTK_OK;
-    if (!d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15)) return NTK_ERR_BAD_ARG;
+    int rc = check_batch_params(t, p);   // the table's path is the byte path: it needs NORMALIZE
+    if (rc || n_bytes == 0) return rc;
+    if ((rc = check_batch_pointers(d_seq, d_qual))) return rc;
     CT_HIPCHK(hipSetDevice(t->device));
     CountArgs a;
     a.seq = d_seq; a.n_bytes = n_bytes; a.k = t->k;

@@ -50,22 +50,10 @@ CALLS = {
 # every symbol include/needletail_amd_minhash.h declares
 SYMBOLS = [PREFIX + c for c in CALLS]
 
-_minhash_lib = None
-
 
 def lib() -> C.CDLL:
     """The MinHash library with its calls typed; loaded once."""
-    global _minhash_lib
-    if _minhash_lib is None:
-        L.lib()   # the core library first: the MinHash library links against it
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()')")
-        X = C.CDLL(LIB_PATH)
-        for call, argtypes in CALLS.items():
-            getattr(X, PREFIX + call).argtypes = argtypes
-        getattr(X, PREFIX + "destroy").restype = None
-        _minhash_lib = X
-    return _minhash_lib
+    return L.load(LIB_PATH, PREFIX, CALLS)
 
 
 def _u64_array(a, what: str):
@@ -94,9 +82,11 @@ def compare(a, ca, b, cb, num: int = 0, max_hash: int = ALL) -> dict:
     return {name: (float if t is C.c_double else int)(getattr(out, name)) for name, t in Comparison._fields_}
 
 
-class KmerMinHash:
+class KmerMinHash(L.Handle):
     """A MinHash sketch of the k-mers of `path` (a PATH_* constant): k = 1..32 on any path, k = 33..63 on PATH_BYTES_CANONICAL.
     Exactly one of `num` (bottom-s) and `scaled` (every hash <= (2^64 - 1) // scaled) is non-zero."""
+
+    _lib, _prefix = staticmethod(lib), PREFIX
 
     def __init__(self, k: int, path: int, num: int = 0, scaled: int = 0, ctx: Context = None, buffer_entries: int = 0):
         self.ctx = ctx if ctx is not None else default_context()
@@ -104,26 +94,6 @@ class KmerMinHash:
         self.max_hash = ALL // scaled if scaled else ALL
         self._h = C.c_void_p()
         self._check("create", self.ctx._h, k, path, num, scaled, buffer_entries, C.byref(self._h))
-
-    def _check(self, call: str, *args):
-        L.check(getattr(lib(), PREFIX + call)(*args), PREFIX + call)
-
-    def close(self):
-        if self._h:
-            lib().ntk_minhash_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def reset(self):
         self._check("reset", self._h)

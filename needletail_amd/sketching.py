@@ -43,22 +43,10 @@ CALLS = {
 # every symbol include/needletail_amd_sketch.h declares
 SYMBOLS = [PREFIX + c for c in CALLS]
 
-_sketch_lib = None
-
 
 def lib() -> C.CDLL:
     """The sketch library with its calls typed; loaded once."""
-    global _sketch_lib
-    if _sketch_lib is None:
-        L.lib()   # the core library first: the sketch library links against it
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()')")
-        X = C.CDLL(LIB_PATH)
-        for call, argtypes in CALLS.items():
-            getattr(X, PREFIX + call).argtypes = argtypes
-        getattr(X, PREFIX + "destroy").restype = None
-        _sketch_lib = X
-    return _sketch_lib
+    return L.load(LIB_PATH, PREFIX, CALLS)
 
 
 def _checked_registers(regs) -> np.ndarray:
@@ -89,34 +77,16 @@ def estimate_from_registers(regs, n_windows: int, k: int) -> dict:
     return {"distinct": e, "n_windows": int(n_windows), "capacity": max(cap, 1), "zero_registers": int(c[0])}
 
 
-class KmerSketch:
+class KmerSketch(L.Handle):
     """A sketch of the distinct k-mers of `path` (a PATH_* constant): k = 1..32 on any path, k = 33..63 on PATH_BYTES_CANONICAL."""
+
+    _lib, _prefix = staticmethod(lib), PREFIX
 
     def __init__(self, k: int, path: int, ctx: Context = None):
         self.ctx = ctx if ctx is not None else default_context()
         self.k, self.path = k, path
         self._h = C.c_void_p()
         self._check("create", self.ctx._h, k, path, C.byref(self._h))
-
-    def _check(self, call: str, *args):
-        L.check(getattr(lib(), PREFIX + call)(*args), PREFIX + call)
-
-    def close(self):
-        if self._h:
-            lib().ntk_kmer_sketch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def reset(self):
         self._check("reset", self._h)

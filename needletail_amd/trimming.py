@@ -14,8 +14,7 @@ import numpy as np
 
 from . import _lib as L
 from . import counting
-from .abundance import upload_records_with_offsets
-from .counting import KmerTable
+from .counting import KmerTable, upload_records_with_offsets
 from .engine import _ptr
 from .wide_counting import WideKmerTable
 
@@ -39,31 +38,21 @@ CALLS = {
 # every symbol include/needletail_amd_trim.h declares
 SYMBOLS = [PREFIX + c for c in CALLS]
 
-_trim_lib = None
-
 
 def lib() -> C.CDLL:
     """The trim library with its calls typed; loaded once."""
-    global _trim_lib
-    if _trim_lib is None:
-        counting.lib()   # the core and the count library first: the trim library links against both
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build the HIP extensions first (python -c 'import __graft_entry__ as g; g.build()')")
-        X = C.CDLL(LIB_PATH)
-        for call, argtypes in CALLS.items():
-            getattr(X, PREFIX + call).argtypes = argtypes
-        getattr(X, PREFIX + "destroy").restype = None
-        _trim_lib = X
-    return _trim_lib
+    return L.load(LIB_PATH, PREFIX, CALLS, needs=(counting.lib,))
 
 
 def _mode(mode) -> int:
     return MODES[mode] if isinstance(mode, str) else int(mode)
 
 
-class ReadTrimmer:
+class ReadTrimmer(L.Handle):
     """Per-record kept intervals against `table`, a KmerTable (k <= 32), which it borrows (keep the table open while this is), and
     the kept reads as a device batch."""
+
+    _lib, _prefix = staticmethod(lib), PREFIX
 
     def __init__(self, table: KmerTable):
         if isinstance(table, WideKmerTable):
@@ -74,26 +63,6 @@ class ReadTrimmer:
         self.k, self.path = table.k, table.path
         self._h = C.c_void_p()
         self._check("create", self.ctx._h, table._h, C.byref(self._h))
-
-    def _check(self, call: str, *args):
-        L.check(getattr(lib(), PREFIX + call)(*args), PREFIX + call)
-
-    def close(self):
-        if self._h:
-            lib().ntk_read_trim_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def release(self):
         """Free the scratch kept between calls."""

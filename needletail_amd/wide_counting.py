@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _lib as L
-from .counting import CALLS, CountTable, load
+from .counting import CALLS, CountTable
 
 LIB_PATH = os.path.join(L._HERE, "libneedletail_amd_wide_count.so")
 PREFIX = "ntk_wide_table_"
@@ -24,7 +24,7 @@ K_MIN, K_MAX = 33, 63
 
 
 def lib():
-    return load(LIB_PATH, PREFIX)
+    return L.load(LIB_PATH, PREFIX, CALLS)
 
 
 _CODE = np.full(256, 255, dtype=np.uint8)
@@ -70,7 +70,7 @@ class WideKmerTable(CountTable):
     lookup() takes k-mers as str / bytes (either strand) or as an (n, 2) array of [hi, lo] rows (canonicalised by the library); one
     k-mer given as str / bytes reads an int."""
 
-    _lib_path, _prefix, _key_words = LIB_PATH, PREFIX, 2
+    _lib, _prefix, _key_words = staticmethod(lib), PREFIX, 2
 
     def _queries(self, kmers):
         if isinstance(kmers, (bytes, bytearray, str)):

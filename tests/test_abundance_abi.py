@@ -18,6 +18,7 @@ LIBDIR = os.path.join(ROOT, "needletail_amd")
 SO = os.path.join(LIBDIR, "libneedletail_amd_abundance.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_abundance.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_abundance.hip")
+CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 GPU_TESTS = "test_gpu_abundance.py"
 OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so")
 
@@ -105,8 +106,9 @@ def test_kernel_constants_are_the_tests():
     """The GPU tests aim at the wave kernel's register seam, the long-record threshold and the chunk length; hold them to the source."""
     import _count_model as CM
     src = open(HIP).read()
-    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", src)
+    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", open(CHUNKS).read())
     assert int(chunk.group(1)) << int(chunk.group(2)) == CM.CHUNK
+    assert not re.search(r"kChunkBases\s*=", src), "the chunk length is ntk_chunks.hpp's alone"
     assert int(re.search(r"kRegRounds = (\d+);", src).group(1)) * 64 == A_REG_WINDOWS
     assert int(re.search(r"kLongRecord = (\d+);", src).group(1)) == A_LONG_RECORD
     assert not re.search(r"\basm\b|__asm", src), "plain HIP C++"

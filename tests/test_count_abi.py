@@ -18,7 +18,12 @@ CORE = os.path.join(ROOT, "needletail_amd", "libneedletail_amd.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_count.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_count.hip")
 WIDE_HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_count.hip")
-COMMON = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_count_common.hpp")   # what the narrow and the wide table share
+CSRC = os.path.join(ROOT, "needletail_amd", "csrc")
+COMMON = os.path.join(CSRC, "ntk_count_common.hpp")   # what the narrow and the wide table share
+CONSUMER = os.path.join(CSRC, "ntk_consumer.hpp")     # what every library on the core's ABI shares
+CHUNKS = os.path.join(CSRC, "ntk_chunks.hpp")         # the chunk geometry
+# the six library sources
+SOURCES = [os.path.join(CSRC, f"ntk_{name}.hip") for name in ("count", "wide_count", "sketch", "abundance", "trim", "minhash")]
 
 # every kernel of the count library with the test that launches it (file, test function); rocPRIM's sort kernels by namespace
 COUNT_KERNELS = {
@@ -89,26 +94,31 @@ def test_every_kernel_names_the_test_that_launches_it():
 
 
 def test_product_files_never_name_the_checker():
-    for path in (HEADER, HIP, COMMON, os.path.join(ROOT, "needletail_amd", "counting.py"), os.path.join(ROOT, "examples", "count_kmers.cpp")):
+    for path in (HEADER, HIP, COMMON, CONSUMER, CHUNKS, os.path.join(ROOT, "needletail_amd", "counting.py"), os.path.join(ROOT, "examples", "count_kmers.cpp")):
         txt = open(path).read()
         assert not re.search(r"\boracle\b|ntko_", txt), path
 
 
 def test_the_shared_pieces_are_defined_once():
-    """The hash, the reductions, the host helpers and the extract count / scan and spectrum kernels live in ntk_count_common.hpp only:
-    neither table's source defines its own copy again."""
-    shared = ("fmix64", "wave_sum", "add_agent", "block_sum_u32", "grid_for", "alloc_status")
+    """The hash, the reductions, the host helpers, the record rule and the chunk walk live in ntk_consumer.hpp only, the extract count /
+    scan and spectrum kernels in ntk_count_common.hpp only: none of the six library sources defines its own copy again."""
+    shared = ("fmix64", "wave_sum", "add_agent", "block_sum_u32", "grid_for", "alloc_status", "record_span", "uniform", "for_each_chunk")
     kernel = r"__global__[^{;]*?\bvoid\s+\w*(?:extract_count|extract_scan|spectrum)_kernel\s*\("
-    common = open(COMMON).read()
+    common, consumer = open(COMMON).read(), open(CONSUMER).read()
     for name in shared:
-        assert re.search(rf"\b{name}\([^)]*\)\s*\{{", common), (name, "not defined in ntk_count_common.hpp")
-    assert len(re.findall(kernel, common)) == 3
-    for path in (HIP, WIDE_HIP):
+        assert re.search(rf"\b{name}\([^)]*\)\s*\{{", consumer), (name, "not defined in ntk_consumer.hpp")
+        assert not re.search(rf"\b{name}\([^)]*\)\s*\{{", common), (name, "defined again in ntk_count_common.hpp")
+    assert re.search(r"struct MaterialiseScratch \{", consumer) and '#include "ntk_consumer.hpp"' in common
+    assert len(re.findall(kernel, common)) == 3 and not re.search(kernel, consumer)
+    for path in SOURCES:
         src = open(path).read()
         for name in shared:
             assert not re.search(rf"\b{name}\([^)]*\)\s*\{{", src), (name, "defined again in", path)
         assert not re.search(kernel, src), ("an extract count / scan or spectrum kernel defined again in", path)
-        assert '#include "ntk_count_common.hpp"' in src, path
+        assert not re.search(r"struct MaterialiseScratch\b", src), path
+        # the two tables take the shared pieces through their own header, the other four directly
+        want = "ntk_count_common.hpp" if path in (HIP, WIDE_HIP) else "ntk_consumer.hpp"
+        assert f'#include "{want}"' in src, path
 
 
 def test_no_device_is_a_loud_error():
@@ -183,15 +193,16 @@ def test_model_sizing_rule():
 def test_table_hash_probe_bound_and_chunk_are_the_models():
     """The edge tests aim keys at home slots and records at chunk seams with tests/_count_model.py.  If the table's hash, probe
     bound or chunk length changes, say so here, on the CPU, rather than as a puzzling count mismatch on the GPU."""
-    src, common = open(HIP).read(), open(COMMON).read()
-    m = re.search(r"inline uint64_t fmix64\(uint64_t x\)\s*\{(.*?)\}", common, re.S)
-    assert m, "fmix64 not found in ntk_count_common.hpp"
+    src, common, consumer = open(HIP).read(), open(COMMON).read(), open(CONSUMER).read()
+    m = re.search(r"inline uint64_t fmix64\(uint64_t x\)\s*\{(.*?)\}", consumer, re.S)
+    assert m, "fmix64 not found in ntk_consumer.hpp"
     steps = re.findall(r"x \^= x >> (\d+);|x \*= (0x[0-9a-fA-F]+)ull;", m.group(1))
     got = [int(a) if a else int(b, 16) for a, b in steps]
     want = [M.FMIX_SHIFT, M.FMIX_MUL[0], M.FMIX_SHIFT, M.FMIX_MUL[1], M.FMIX_SHIFT]
-    assert got == want, f"ntk_count_common.hpp's fmix64 is {got}, tests/_count_model.py's is {want}: update the model with the hash"
+    assert got == want, f"ntk_consumer.hpp's fmix64 is {got}, tests/_count_model.py's is {want}: update the model with the hash"
     assert re.search(r"fmix64\(key\) & a\.mask", src) and re.search(r"fmix64\(q\) & mask", src), "home slot is not fmix64 & mask"
     assert len(re.findall(r"slot = \(slot \+ 1\) & (?:a\.)?mask", src)) == 2, "probing is not linear with wrap-around"
     assert int(re.search(r"kProbeMax = (\d+);", common).group(1)) == M.PROBE_MAX
-    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", src)
+    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", open(CHUNKS).read())
     assert int(chunk.group(1)) << int(chunk.group(2)) == M.CHUNK
+    assert not re.search(r"kChunkBases\s*=", src), "the chunk length is ntk_chunks.hpp's alone"

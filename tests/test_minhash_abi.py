@@ -22,6 +22,7 @@ HEADER = os.path.join(ROOT, "include", "needletail_amd_minhash.h")
 SKETCH_HEADER = os.path.join(ROOT, "include", "needletail_amd_sketch.h")
 CSRC = os.path.join(ROOT, "needletail_amd", "csrc")
 HIP, WALK_HPP = os.path.join(CSRC, "ntk_minhash.hip"), os.path.join(CSRC, "ntk_wide_walk.hpp")
+CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 SKETCH_HIP, WIDE_HIP = os.path.join(CSRC, "ntk_sketch.hip"), os.path.join(CSRC, "ntk_wide_count.hip")
 GPU_TESTS = "test_gpu_minhash.py"
 OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so",
@@ -148,9 +149,10 @@ def test_minhash_constants_are_the_sketchs_and_the_models():
     for text, name in ((src, "minhash_hash"), (sk_src, "sketch_hash")):
         assert re.search(name + r"\(uint64_t key\) \{ return fmix64\(key \^ kXor\); \}", text)
         assert re.search(name + r"\(uint64_t hi, uint64_t lo\) \{ return fmix64\(lo \^ fmix64\(hi\) \^ kXor\); \}", text)
-    assert '#include "ntk_count_common.hpp"' in src and not re.search(r"\bfmix64\([^)]*\)\s*\{", src), "fmix64 defined again"
-    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", src)
+    assert '#include "ntk_consumer.hpp"' in src and not re.search(r"\bfmix64\([^)]*\)\s*\{", src), "fmix64 defined again"
+    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", open(CHUNKS).read())
     assert int(chunk.group(1)) << int(chunk.group(2)) == M.CHUNK == S.CHUNK == CM.CHUNK
+    assert not re.search(r"kChunkBases\s*=", src), "the chunk length is ntk_chunks.hpp's alone"
     assert int(re.search(r"#define NTK_MINHASH_MAX_NUM \(1ull << (\d+)\)", hdr).group(1)) == 20
     assert int(re.search(r"#define NTK_MINHASH_BUFFER_DEFAULT \(1ull << (\d+)\)", hdr).group(1)) == 22
     assert int(re.search(r"#define NTK_MINHASH_BUFFER_MIN (\d+)ull", hdr).group(1)) == M.BUFFER_MIN == M.LANE_RUN

@@ -20,6 +20,7 @@ LIBDIR = os.path.join(ROOT, "needletail_amd")
 SO = os.path.join(LIBDIR, "libneedletail_amd_sketch.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_sketch.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_sketch.hip")
+CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 WIDE_HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_count.hip")
 GPU_TESTS = "test_gpu_sketch.py"
 
@@ -119,9 +120,10 @@ def test_sketch_constants_are_the_models():
     assert re.search(r"sketch_slot\(uint64_t h\) \{ return \(uint32_t\)\(h >> \(64 - kP\)\); \}", src)
     assert re.search(r"sketch_rank\(uint64_t h\) \{ return \(uint32_t\)__builtin_clzll\(\(h << kP\) \| \(\(uint64_t\)1 << \(kP - 1\)\)\) \+ 1; \}", src)
     # the tables' hash, defined once, in the shared header
-    assert '#include "ntk_count_common.hpp"' in src and not re.search(r"\bfmix64\([^)]*\)\s*\{", src), "fmix64 defined again"
-    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", src)
+    assert '#include "ntk_consumer.hpp"' in src and not re.search(r"\bfmix64\([^)]*\)\s*\{", src), "fmix64 defined again"
+    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", open(CHUNKS).read())
     assert int(chunk.group(1)) << int(chunk.group(2)) == S.CHUNK == CM.CHUNK
+    assert not re.search(r"kChunkBases\s*=", src), "the chunk length is ntk_chunks.hpp's alone"
     assert int(re.search(r"kSketchThreads = (\d+);", src).group(1)) == S.THREADS
     # the wide walker restates wt_count_kernel's: the same lane geometry, k range and per-byte rules as ntk_wide_count.hip
     for text in (src, wide):

@@ -19,6 +19,7 @@ LIBDIR = os.path.join(ROOT, "needletail_amd")
 SO = os.path.join(LIBDIR, "libneedletail_amd_trim.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_trim.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_trim.hip")
+CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 RUNS_HPP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_trim_runs.hpp")
 GPU_TESTS = "test_gpu_trim.py"
 OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so",
@@ -119,8 +120,9 @@ def test_kernel_constants_are_the_tests():
     """The GPU tests aim at the group / wave seam of the interval kernel, the long-record threshold of the copy and the chunk length."""
     import _count_model as CM
     src = open(HIP).read()
-    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", src)
+    chunk = re.search(r"kChunkBases = \(uint64_t\)(\d+) << (\d+);", open(CHUNKS).read())
     assert int(chunk.group(1)) << int(chunk.group(2)) == CM.CHUNK
+    assert not re.search(r"kChunkBases\s*=", src), "the chunk length is ntk_chunks.hpp's alone"
     group, rounds = (int(re.search(rf"{name} = (\d+);", src).group(1)) for name in ("kGroup", "kGroupRounds"))
     assert group * rounds == T_GROUP_WORDS and 64 % group == 0
     assert int(re.search(r"kLongPieces = (\d+);", src).group(1)) == T_LONG_PIECES
@@ -134,9 +136,9 @@ def test_scratch_bound_arithmetic():
     8 B per 16 384 bases + 16 B for the list of long records."""
     import _count_model as CM
     src, hdr = open(HIP).read(), re.sub(r"\s*\n \*\s*", " ", open(HEADER).read())
-    assert re.search(r"ntk_kmer_table_lookup_device\(t->table, t->scratch\.d_values \+ skip, end - start, t->d_counts\)", src)
-    assert re.search(r"grow\(t->d_counts, t->chunk_bases, \(chunk \+ 15\) & ~\(uint64_t\)15, sizeof\(uint64_t\)\)", src)
-    assert re.search(r"chunk = n_bytes < kChunkBases \? n_bytes : kChunkBases;", src)
+    assert re.search(r"ntk_kmer_table_lookup_device\(t->table, t->scratch\.d_values \+ c\.skip\(\), c\.end - c\.start, t->d_counts\)", src)
+    assert re.search(r"grow\(t->d_counts, t->chunk_bases, \(chunk_bases\(n_bytes\) \+ 15\) & ~\(uint64_t\)15, sizeof\(uint64_t\)\)", src)
+    assert re.search(r"uint64_t chunk_bases\(uint64_t n_bytes\) \{ return n_bytes < kChunkBases \? n_bytes : kChunkBases; \}", open(CHUNKS).read())
     assert re.search(r"uint64_t planes_words\(uint64_t n_bytes\) \{ return \(n_bytes \+ 63\) / 64 \+ 1; \}", src)
     assert re.search(r"grow\(t->d_scan, t->scan_items, n_records \+ 1, sizeof\(ScanItem\)\)", src)
     assert re.search(r"grow\(t->d_long, t->long_cap, \(n_bytes >> 14\) \+ 2, sizeof\(uint64_t\)\)", src)

@@ -19,6 +19,7 @@ SO = os.path.join(ROOT, "needletail_amd", "libneedletail_amd_wide_count.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_wide_count.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_count.hip")
 COMMON = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_count_common.hpp")   # what the narrow and the wide table share
+CONSUMER = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_consumer.hpp")    # what every library on the core's ABI shares
 GPU_TESTS = "test_gpu_wide_count.py"
 
 # every kernel of the wide count library with the test that launches it; rocPRIM's sort kernels by namespace
@@ -82,7 +83,7 @@ def test_every_kernel_names_the_test_that_launches_it():
 
 
 def test_product_files_never_name_the_checker():
-    for path in (HEADER, HIP, COMMON, os.path.join(ROOT, "needletail_amd", "wide_counting.py")):
+    for path in (HEADER, HIP, COMMON, CONSUMER, os.path.join(ROOT, "needletail_amd", "wide_counting.py")):
         txt = open(path).read()
         assert not re.search(r"\boracle\b|ntko_", txt), path
 
@@ -104,9 +105,9 @@ def test_no_device_is_a_loud_error():
 def test_table_hash_probe_bound_and_lane_geometry_are_the_models():
     """The GPU tests aim keys at home slots and records at lane-run seams with tests/_wide_count_model.py.  If the table's hash, probe
     bound or the count kernel's geometry changes, say so here, on the CPU, rather than as a puzzling count mismatch on the GPU."""
-    src, common = open(HIP).read(), open(COMMON).read()
-    m = re.search(r"inline uint64_t fmix64\(uint64_t x\)\s*\{(.*?)\}", common, re.S)
-    assert m, "fmix64 not found in ntk_count_common.hpp"
+    src, common, consumer = open(HIP).read(), open(COMMON).read(), open(CONSUMER).read()
+    m = re.search(r"inline uint64_t fmix64\(uint64_t x\)\s*\{(.*?)\}", consumer, re.S)
+    assert m, "fmix64 not found in ntk_consumer.hpp"
     steps = re.findall(r"x \^= x >> (\d+);|x \*= (0x[0-9a-fA-F]+)ull;", m.group(1))
     got = [int(a) if a else int(b, 16) for a, b in steps]
     assert got == [CM.FMIX_SHIFT, CM.FMIX_MUL[0], CM.FMIX_SHIFT, CM.FMIX_MUL[1], CM.FMIX_SHIFT], got
@@ -116,7 +117,7 @@ def test_table_hash_probe_bound_and_lane_geometry_are_the_models():
     assert int(re.search(r"kProbeMax = (\d+);", common).group(1)) == W.PROBE_MAX
     assert int(re.search(r"kLaneRun = (\d+);", src).group(1)) == W.LANE_RUN
     assert int(re.search(r"kPrime = (\d+);", src).group(1)) == W.PRIME
-    assert int(re.search(r"kThreads = (\d+);", common).group(1)) == W.THREADS
+    assert int(re.search(r"kThreads = (\d+);", consumer).group(1)) == W.THREADS
     assert re.search(r"kKMin = (\d+), kKMax = (\d+);", src).groups() == (str(W.K_MIN), str(W.K_MAX))
 
 

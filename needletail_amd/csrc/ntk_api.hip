@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ntk_kernels.hpp"
+#include "ntk_plan.hpp"
 
 using namespace ntk;
 
@@ -218,11 +219,7 @@ int resolve_mode(const ntk_params *p, bool batch_face, Mode *m)
 // a template constant: the window-mask algebra indexes lane masks by k; ntk_scan2.hip).  Materialise mode: the round-1 scan_kernel with
 // k at run time, plus a k = 21 build for the canonical paths (-5 %); it runs at the rate of a plain read-1-write-8 expansion kernel
 // (2.45 ms per 1.51 GB of input against 2.45-2.50 ms, profiles/r04b/wbw.txt), i.e. it is bound by the 8 bytes it writes per position.
-constexpr int kMaxShards = 256;      // work counters: the pull atomics of > 6000 waves on 8 counters were the bottleneck (profiles/r02)
 constexpr uint32_t kLowerRing = 64;  // "a lower-case byte was seen" flags of consecutive speculative launches (each launch clears its successor's)
-// a launch of a tile scan covers at most this many tiles, a shard <= 2^22 of them, so that the per-block u32 histogram cells (a block can at
-// most drain its whole shard: 2^22 * 992 windows), the u32 work counters and 32-bit buffer offsets cannot overflow
-constexpr uint64_t kMaxTilesPerLaunch = (uint64_t)8 << 22;
 
 // The round-1 scan_kernel, materialise mode only (QM names a template argument).
 // (no TIE_RC && !ACCEPT_U build: that is the byte path on input that was not normalised, which materialise mode rejects - run_scan)
@@ -423,43 +420,37 @@ int run_bytes_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_par
 
 // One scan of a pull-model kernel that takes a ScanArgs (scan_kernel, scan2_kernel, minimizer_scan_kernel) over a.seq[0, a.n_bytes).
 // The caller picks the build and its geometry (TileScan) and fills what is its own in `a`: k, window, quality stream, output planes.
-// Everything else is done here, once: the launch ranges of at most kMaxTilesPerLaunch tiles, shards and tiles per pull, the work counters,
-// zero_acc on the first launch only, the partials, the timed span and - in reduce mode - the fold.
+// Everything else is done here, once: the launch ranges of at most kMaxTilesPerLaunch tiles, shards and tiles per pull (plan_launch,
+// ntk_plan.hpp), the work counters, zero_acc on the first launch only, the partials, the timed span and - in reduce mode - the fold.
 struct TileScan {
     const void *fn = nullptr;
     int threads = 0;
     size_t lds = 0;           // dynamic LDS per block
-    uint32_t halo_lanes = 0;  // a tile emits 64 - halo_lanes slots of 16 positions
+    uint32_t stride = 0;      // bytes a tile advances by = window ends it emits: the build's own (Sv2Geom<..>::kStride, kTileStride, ...)
     uint64_t max_chunk = 0;   // cap on tiles per pull
     int max_per_cu = 0;       // cap on resident blocks per CU; the auto grid is exactly the resident blocks (work is pulled: more only write empty histograms, +1.5 %)
     bool reduce = true;       // partials + fold; a materialise scan has neither
     bool speculate = false;   // the SPEC build on un-normalised byte-path input: canonical_bytes_reduce_kernel<false> is queued behind the scan,
     uint32_t cutoff = 0;      // ... masking a.qual at this cutoff (0: no quality stream)
 };
-inline uint64_t tile_count(uint64_t n, uint64_t tile_slots) { return ((n + 15) / 16 + tile_slots - 1) / tile_slots; }
 int launch_tile_scan(ntk_ctx *c, const TileScan &s, ScanArgs &a, bool zero_first)   // zero_first: the first launch zeroes the accumulators in its prologue
 {
     int per_cu = 0, rc = resident_blocks(c, s.fn, s.threads, s.lds, s.max_per_cu, &per_cu);
     if (rc) return rc;
     const uint64_t blocks_max = block_cap(c, per_cu), waves_per_block = (uint64_t)s.threads / 64;
-    const uint64_t tile_slots = 64 - (uint64_t)s.halo_lanes, tile_stride = tile_slots * 16, n = a.n_bytes;
+    const uint64_t n = a.n_bytes;
     const int blocks_raw = s.speculate ? raw_bytes_blocks(c, n) : 0;
-    a.n_tiles = tile_count(n, tile_slots);
+    a.n_tiles = tile_count(n, s.stride);
     a.work_counters = c->d_work;
     a.zero_words = NTK_ACC_WORDS;
     for (uint64_t tb = 0; tb < a.n_tiles; tb += kMaxTilesPerLaunch) {
-        const uint64_t te = tb + kMaxTilesPerLaunch < a.n_tiles ? tb + kMaxTilesPerLaunch : a.n_tiles;
-        const uint64_t tiles = te - tb;
-        uint64_t chunk = tiles / (blocks_max * waves_per_block * 4);  // >= ~4 pulls per wave, <= max_chunk tiles each (8..32 are within 1 %: profiles/r02c)
-        chunk = chunk < 1 ? 1 : (chunk > s.max_chunk ? s.max_chunk : chunk);
-        const uint64_t want_blocks = (tiles + chunk * waves_per_block - 1) / (chunk * waves_per_block);
-        const int blocks = (int)(want_blocks < blocks_max ? want_blocks : blocks_max);
-        a.tile_begin = tb; a.tile_end = te;
-        const uint64_t first_tail = n / tile_stride;   // tiles t with (t + 1) * tile_stride > n_bytes touch the end of the input
-        a.tail_tile_rel = first_tail < tb ? 0u : (first_tail - tb > 0xFFFFFFFEull ? 0xFFFFFFFFu : (uint32_t)(first_tail - tb));
-        a.n_shards = blocks < kMaxShards ? (uint32_t)blocks : (uint32_t)kMaxShards;
-        a.tiles_per_shard = (uint32_t)((tiles + a.n_shards - 1) / a.n_shards);
-        a.chunk_tiles = (uint32_t)chunk;
+        const LaunchPlan lp = plan_launch(n, s.stride, tb, blocks_max, waves_per_block, s.max_chunk);
+        const int blocks = (int)lp.blocks;
+        a.tile_begin = lp.tile_begin; a.tile_end = lp.tile_end;
+        a.tail_tile_rel = lp.tail_tile_rel;
+        a.n_shards = lp.n_shards;
+        a.tiles_per_shard = lp.tiles_per_shard;
+        a.chunk_tiles = lp.chunk_tiles;
         a.zero_acc = zero_first ? c->d_acc : nullptr;
         zero_first = false;
         // the work counters are zero on entry: the fold of the previous reduce scan re-armed them (launch_fold); anything else
@@ -494,7 +485,7 @@ int launch_tile_scan(ntk_ctx *c, const TileScan &s, ScanArgs &a, bool zero_first
 // The k-mer scans (reduce and materialise) and the register-fused minimizer builds of scan2_kernel.
 int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, const Mode &m, bool reduce,
              uint64_t *d_values, uint16_t *d_valid16, uint16_t *d_rc16, const uint8_t *d_qual = nullptr, const void *fused_min_fn = nullptr,
-             int halo_lanes = kHaloLanes)   // 3 for the fused-minimizer builds whose windows need more than 32 bytes (ntk_tile.hpp Sv2Geom)
+             uint32_t fused_w = 0)   // the window length of a fused-minimizer build: its tile geometry differs (ntk_tile.hpp Sv2Geom)
 {
     const bool zero_first = reduce && (p->flags & NTK_FLAG_RESET);
     if (n == 0) {
@@ -503,6 +494,9 @@ int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, 
     }
     if (bad_device_input(d_seq, d_qual)) return NTK_ERR_BAD_ARG;
     const uint32_t cutoff = d_qual ? quality_cutoff(p) : 0u;  // cutoff 0 masks nothing: the plain build runs
+    // the stride of the build that runs, from the geometry it was compiled with: a scan2 build in reduce mode (k <= 32: larger k leaves through
+    // run_bytes_reduce below), scan_kernel in materialise mode
+    const uint32_t stride = !reduce ? (uint32_t)kTileStride : (p->k <= 32 ? (uint32_t)sv2_stride_bytes((int)(fused_w ? p->k + fused_w - 1 : p->k), fused_w == 0) : 0u);
     bool speculate = false;
     if (m.raw_bytes) {
         // byte path on input that was not normalised: reduce mode only; dense values and windowed minimizers on such input are not built
@@ -516,7 +510,7 @@ int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, 
         // bit 5), the raw-byte kernel is queued behind it and returns at once unless the flag went up, and the fold takes whichever partials
         // are valid: no host round trip, 0.45 ms instead of 5.1 per 1.5 GB of upper-case reads.  One launch only (the raw-byte kernel works on
         // window starts, the scan on window ends: their launch ranges do not line up), the direct route otherwise and under NTK_ROUTE_NO_SPECULATION.
-        speculate = p->k <= 32 && tile_count(n, 64 - (uint64_t)halo_lanes) <= kMaxTilesPerLaunch && !(c->route_off & NTK_ROUTE_NO_SPECULATION);
+        speculate = p->k <= 32 && tile_count(n, stride) <= kMaxTilesPerLaunch && !(c->route_off & NTK_ROUTE_NO_SPECULATION);
         if (!speculate) return run_bytes_reduce(c, d_seq, n, p, zero_first, m.accept_u, qual, cutoff);   // (accept_u: only k > 32 comes here normalised)
     }
     const void *fn = fused_min_fn ? fused_min_fn : pick_scan(m, p->k, reduce, cutoff != 0);   // (speculate: tie_rc, !accept_u - the SPEC build)
@@ -543,7 +537,7 @@ int run_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params *p, 
     // Reduce builds: two blocks of `threads` (768, or 640 / 512 for a build above 80 VGPRs: chosen above) per CU, each with its 64 KiB LDS
     // histogram, <= 24 tiles per pull; materialise stages 8.7 KiB per wave through LDS: 256-thread blocks, 4 per CU.
     TileScan s;
-    s.fn = fn; s.threads = threads; s.halo_lanes = (uint32_t)halo_lanes; s.max_chunk = 24;
+    s.fn = fn; s.threads = threads; s.stride = stride; s.max_chunk = 24;
     s.lds = reduce ? 0 : (size_t)(threads / 64) * kStageWaveU64 * sizeof(uint64_t);
     s.max_per_cu = reduce ? 2 * (1024 / threads) : 4;
     s.reduce = reduce; s.speculate = speculate; s.cutoff = cutoff;
@@ -590,7 +584,7 @@ int run_min_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params 
     s.fn = pick_min_generic(m, cutoff != 0, f64, p->k);
     if (!s.fn) return NTK_ERR_BAD_ARG;
     s.threads = min_gen_threads(f64);   // 512: two blocks per CU, 768: one (ntk_kernels.hpp), each with its 64 KiB LDS histogram
-    s.halo_lanes = a.min_halo_lanes; s.max_chunk = 16; s.max_per_cu = 8;
+    s.stride = (64u - a.min_halo_lanes) * 16u; s.max_chunk = 16; s.max_per_cu = 8;
     return launch_tile_scan(c, s, a, (p->flags & NTK_FLAG_RESET) != 0);
 }
 
@@ -1724,7 +1718,7 @@ static int minimizers_reduce_impl(ntk_ctx *c, const uint8_t *d_seq, const uint8_
         const bool masked = d_qual && quality_cutoff(p);
         const void *fn = (c->route_off & NTK_ROUTE_NO_REGFUSED) ? nullptr : pick_scan_min(m, p->k, w, masked);   // (route bits: ntk_ctx_set_option)
         if (fn)
-            return run_scan(c, d_seq, n, p, m, true, nullptr, nullptr, nullptr, masked ? d_qual : nullptr, fn, p->k + w - 1 > 32 ? 3 : 2);
+            return run_scan(c, d_seq, n, p, m, true, nullptr, nullptr, nullptr, masked ? d_qual : nullptr, fn, w);
         // every other (k <= 31, w <= 49): the generic fused kernel (one pass as well, run-time k and w)
         if (p->k <= 31 && w <= 49 && !(c->route_off & NTK_ROUTE_NO_GENERIC))
             return run_min_scan(c, d_seq, n, p, m, w, masked ? d_qual : nullptr);

@@ -20,7 +20,7 @@
 // by design and measure what a class of the tile loop costs (profiles/r03c/ablation.txt, r04i/ablation.txt).  No product object may see one.
 #if !defined(NTK_KBENCH) && (defined(NTK_ABL_LOADSONLY) || defined(NTK_ABL_FLOOR) || defined(NTK_ABL_NOLDS) || defined(NTK_ABL_NODIGEST) || \
                              defined(NTK_ABL_NOEXEC) || defined(NTK_ABL_NOSDWA) || defined(NTK_ABL_NOMASKALG) || defined(NTK_V_CLOCKS) || \
-                             defined(NTK_X_CMPFIRST) || defined(NTK_X_TWOPHASE) || defined(NTK_X_MFMASUM) || defined(NTK_X_SELOUT) || defined(NTK_X_PREFETCH2) || defined(NTK_X_FASTSTART) || defined(NTK_ABL_HALFIMPORTS))
+                             defined(NTK_X_CMPFIRST) || defined(NTK_X_TWOPHASE) || defined(NTK_X_MFMASUM) || defined(NTK_X_SELOUT) || defined(NTK_X_PREFETCH2) || defined(NTK_ABL_HALFIMPORTS))
 #error "NTK_ABL_* / NTK_X_* / NTK_V_CLOCKS are kernel-bench switches: build with -DNTK_KBENCH (tools/build_kbench.sh), never into the library"
 #endif
 
@@ -283,21 +283,10 @@ struct DevMasks2 {
     i32x4 macc = {0, 0, 0, 0}, msel = {0, 0, 0, 0};   // kbench experiment: byte sums on the matrix pipe (see emit_canon)
 #endif
 
-    template <int KM, class Enc>   // KM: good bases a window needs (K, or K + W - 1 for windowed minimizers)
+    template <int KM, bool EXACT, class Enc>   // KM: good bases a window needs (K: EXACT, the tile geometry of the k-mer builds - or K + W - 1 for windowed minimizers)
     __device__ __forceinline__ void compute(const Enc &en, bool tail_tile, int64_t lane_base, uint64_t n_bytes)
     {
         uint64_t B[16];
-#ifdef NTK_X_CLEANTILE   // kbench experiment (profiles/r06v): a tile that holds no break at all (long contigs) needs no byte compares and no mask algebra
-        {
-            const uint32_t dif = (en.ex[0] ^ en.uu[0]) | (en.ex[1] ^ en.uu[1]) | (en.ex[2] ^ en.uu[2]) | (en.ex[3] ^ en.uu[3]);
-            if (!tail_tile && __builtin_amdgcn_ballot_w64(dif != 0u) == 0ull) {
-#pragma unroll
-                for (int i = 0; i < 16; i++) { VA[i] = Sv2Geom<KM>::kKeep; VB[i] = ~0ull; }
-                asm volatile("" ::: "memory");
-                return;
-            }
-        }
-#endif
 #ifdef NTK_ABL_NOSDWA
 #pragma unroll
         for (int i = 0; i < 16; i++) B[i] = __builtin_amdgcn_ballot_w64(en.ex[i & 3] != (uint32_t)i);
@@ -322,7 +311,7 @@ struct DevMasks2 {
 #pragma unroll
         for (int i = 0; i < 16; i++) { VA[i] = B[i]; VB[i] = ~0ull; }
 #else
-        window_masks_ab_any<KM>(B, VA, VB);
+        window_masks_ab_any<KM, EXACT>(B, VA, VB);
 #endif
     }
 
@@ -706,7 +695,7 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
     constexpr bool WORD = K <= 16;                        // one-word values (lane_tile_sv2w): digests kept left-aligned
     constexpr bool LIGHT = Sv2Light<K, HB>::value && !WORD;
     constexpr int kCells = 1 << HB;
-    using Geo = Sv2Geom<(W ? K + W - 1 : K)>;   // halo lanes / stride: 2 / 992 bytes; fused minimizers whose windows need more than 32 bytes: 3 / 976
+    using Geo = Sv2Geom<(W ? K + W - 1 : K), (W == 0)>;   // stride / halo bytes: 1025 - K rounded down to a dword / the rest of the 1024 (k = 21: 1004 / 20); K <= 16: 1008 / 16; fused minimizers: 992 / 32, windows of more than 32 bytes 976 / 48
     constexpr uint32_t kStride = Geo::kStride, kHaloB = Geo::kHaloBytes;
     // One LDS object, histogram first: the masked regions address the histogram with the cell's byte offset alone, which
     // is only right while the histogram sits at LDS address 0 (checked below; the kernel has no other LDS object).
@@ -720,13 +709,6 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
     const uint64_t dbg_c0 = clock64(), dbg_w0 = wall_clock64();
     uint32_t dbg_tiles = 0;
 #endif
-#ifndef NTK_X_FASTSTART
-    if (a.zero_acc && blockIdx.x == 0)   // NTK_FLAG_RESET: the accumulators start from zero (see ScanArgs)
-        for (uint32_t i = threadIdx.x; i < a.zero_words; i += blockDim.x) a.zero_acc[i] = 0;
-    for (int i = threadIdx.x; i < kCells; i += blockDim.x) s_hist[i] = 0;
-    __syncthreads();
-
-#endif
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t shard = blockIdx.x % a.n_shards;
@@ -736,15 +718,14 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
     if (shard_end > launch_tiles) shard_end = launch_tiles;
     uint32_t *ctr = a.work_counters + shard * 16;
     const uint32_t shard_tiles = shard_begin < shard_end ? shard_end - shard_begin : 0u;
-#ifdef NTK_X_FASTSTART
-    // round-6 experiment (profiles/r06o): the wave's first pull is in flight while the block zeroes its histogram (128-bit stores)
+    // Prologue: the wave's first pull is in flight while the block zeroes its histogram with 128-bit stores (2.5 us per launch less than zeroing
+    // first with 4-byte stores, profiles/r06o).  NTK_FLAG_RESET: block 0 zeroes the accumulators, which start from zero (see ScanArgs).
     uint32_t next = 0;
     if (lane == 0) next = atomicAdd(ctr, a.chunk_tiles);
     if (a.zero_acc && blockIdx.x == 0)
         for (uint32_t i = threadIdx.x; i < a.zero_words; i += blockDim.x) a.zero_acc[i] = 0;
     for (int i = threadIdx.x; i < kCells / 4; i += blockDim.x) reinterpret_cast<u32x4 *>(s_hist)[i] = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
-#endif
     // SPEC: the byte path's tie rule on bytes nobody normalised (NTK_PATH_BYTES_CANONICAL with pre < NORMALIZE).  The reference compares RAW
     // bytes (src/kmer.rs:121-128), which is the 2-bit order as long as no base is lower case - what Sequence::normalize reports by returning
     // None on a clean read (src/sequence.rs:57-61).  The build ORs every byte it loads into `lc` (two full-rate ops per tile); a wave that saw
@@ -761,10 +742,6 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
     { const int sel = 1 << (8 * (lane & 3)); mp.msel = {sel, sel, sel, sel}; }   // B[k][j] = [k % 4 == j % 4]: column j sums the bytes of significance j % 4
 #endif
 
-#ifndef NTK_X_FASTSTART
-    uint32_t next = 0;
-    if (lane == 0) next = atomicAdd(ctr, a.chunk_tiles);
-#endif
     next = __builtin_amdgcn_readfirstlane(next);
 #ifdef NTK_X_GUIDED   // kbench experiment (profiles/r06q): the pulls shrink over a shard's last stretch (remaining / (2 x the shard's waves), at least 2 tiles)
     uint32_t c_cur = a.chunk_tiles;
@@ -842,7 +819,7 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
             lane_tile_sv2<TIE_RC, K>(sink, xl, mp, fl_code, fl_rcode);
 #else
             const EncSV2 en = encode16_sv2<ACCEPT_U>(raw);
-            mp.template compute<(W ? K + W - 1 : K)>(en, tail, (int64_t)tile_byte - (int64_t)kHaloB + lane * 16, a.n_bytes);
+            mp.template compute<(W ? K + W - 1 : K), (W == 0)>(en, tail, (int64_t)tile_byte - (int64_t)kHaloB + lane * 16, a.n_bytes);
             after_encode();
             if constexpr (W > 0) lane_tile_sv2_min<TIE_RC, K, W>(sink, xl, mp, en.code, en.rcode);
             else if constexpr (WORD) lane_tile_sv2w<TIE_RC, K, FWD>(sink, xl, mp, en.code, en.rcode);
@@ -854,9 +831,25 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
             dbg_tiles++;
 #endif
         };
+        // The input's tile 0 starts kHaloB bytes before the buffer: a lane that lies wholly before it has a wrapped offset beyond num_records
+        // and reads as 0.  Where kHaloB is no multiple of 16 one lane straddles byte 0, and how the hardware checks such an access (the offset
+        // arithmetic does not wrap once the compiler has folded a dword's + 4 i into the instruction) is nothing to rely on: that tile is
+        // loaded dword by dword, each dword from its own offset if that is inside the buffer and from offset 0 otherwise, and the dwords from
+        // before the buffer are then zeroed.
+        auto load_first = [&](__amdgpu_buffer_rsrc_t r_, uint32_t off) {
+            uint32_t d[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int32_t o = (int32_t)off + 4 * i;
+                const uint32_t v = __builtin_amdgcn_raw_buffer_load_b32(r_, o >= 0 ? (uint32_t)o : 0u, 0, 0);
+                d[i] = o >= 0 ? v : 0u;
+            }
+            return u32x4{d[0], d[1], d[2], d[3]};
+        };
+        const bool split_first = kHaloB % 16u != 0u && t0 == 0;   // (wave-uniform)
         // the next tile's load is in flight while the current one is processed
-        u32x4 ta = load_tile(voff), qa = ta;
-        if constexpr (QM) qa = load_qual(voff);
+        u32x4 ta = split_first ? load_first(rs, voff) : load_tile(voff), qa = ta;
+        if constexpr (QM) qa = split_first ? load_first(rq, voff) : load_qual(voff);
         // One tile per trip.  The next tile is loaded into the SAME registers as soon as the encode and the validity compares have
         // consumed the current one - the rest of the tile's work (most of it) hides the latency, and no rotation moves are needed
         // (a separate next-tile buffer loaded at the top of the trip and moved at its end: +2 v_mov_b64, about 1 % slower at k = 21, 23

@@ -18,7 +18,7 @@ constexpr int kHistBins = 4096;
 struct ScanArgs {
     const uint8_t *seq;   // 16-B aligned, readable up to round_up(n_bytes, 16)
     uint64_t n_bytes;
-    uint64_t n_tiles;     // ceil(ceil(n_bytes / 16) / 62): tiles of 62 emitting 16-byte slots
+    uint64_t n_tiles;     // ceil(n_bytes / stride): tile t emits the windows ending in [t stride, (t + 1) stride), the stride is the build's (ntk_plan.hpp)
     uint64_t tile_begin;  // first tile of this launch (a launch covers tiles [tile_begin, tile_end))
     uint64_t tile_end;
     uint32_t *work_counters;  // n_shards counters, 16 u32 apart (one per 64-B line), zeroed before the launch
@@ -760,11 +760,22 @@ inline void scan_args_set_window(ScanArgs &a, uint32_t w)
 // ---------------------------------------------------------------------------------------------
 // OK[j] (window ending at byte j is emitted) = A[j] & B[j] with the last AND left open (A = the lane's own prefix, B = what the previous
 // lanes contribute): the masked region forms exec with that AND itself (s_and_b64 exec, A, B) - one scalar op instead of AND + move.
-// Positive logic; a lane shift fills lane 0 with "not a base", and lanes 0 and 1 (halo lanes) are cleared: all their windows are invalid.
-template <int K>
+// Positive logic; a lane shift fills lane 0 with "not a base".
+// Bytes a tile of the sv2 kernels advances by (Sv2Geom below has the reasoning): km = the bytes a window needs, exact = a k-mer build, which
+// re-reads only what its windows need (false: whole halo lanes - the fused-minimizer builds).
+constexpr int sv2_stride_bytes(int km, bool exact)
+{
+    return km > 32 ? 61 * 16 : (!exact ? 62 * 16 : (km <= 16 ? 63 * 16 : ((kTileBytes - (km - 1)) & ~3)));
+}
+// Whole halo lanes (EXACT = false): lanes 0 and 1 are cleared, all their windows are invalid.  EXACT: the lane shifts of B are all the halo
+// there is - they clear every window that reaches before lane 0: lane 0 always, lane 1 for j < K - 17 - and the kOverlap windows after
+// those, which the previous tile emits, are cleared in B by hand (compile-time masks, at most three scalar ops per tile).
+template <int K, bool EXACT = false>
 NTK_HD void window_masks_ab(const uint64_t (&G)[16], uint64_t (&A)[16], uint64_t (&B)[16])
 {
     static_assert(K >= 17 && K <= 32, "sv path is built for 17 <= k <= 32");
+    constexpr int kOverlap = EXACT ? kTileBytes - sv2_stride_bytes(K, true) - (K - 1) : 0;
+    static_assert(kOverlap >= 0 && K - 17 + kOverlap <= 16, "the overlap windows end in lane 1");
     uint64_t S[16];
     S[15] = G[15];
 #pragma unroll
@@ -774,13 +785,10 @@ NTK_HD void window_masks_ab(const uint64_t (&G)[16], uint64_t (&A)[16], uint64_t
         const int c = 17 + j - K, a_ = c > 0 ? c : 0;
         uint64_t v = S[a_] << 1;
         if (c < 0) v &= S[(33 + j - K) & 15] << 2;
+        if (c >= 0 && c < kOverlap) v &= ~2ull;   // lane 1, bytes K - 17 .. K - 18 + kOverlap: the previous tile's last windows
         B[j] = v;
     }
-#ifdef NTK_X_EXACTHALO   // the lane shifts of B already clear every window that reaches before lane 0: lane 0 always, lane 1 for j < K - 17
-    A[0] = G[0];
-#else
-    A[0] = G[0] & ~3ull;  // halo lanes 0/1: cleared once here, inherited by every prefix
-#endif
+    A[0] = EXACT ? G[0] : G[0] & ~3ull;  // halo lanes 0/1: cleared once here, inherited by every prefix
 #pragma unroll
     for (int j = 1; j < 16; j++) A[j] = A[j - 1] & G[j];
 }
@@ -846,20 +854,28 @@ NTK_HD void window_masks1_ab(const uint64_t (&G)[16], uint64_t (&A)[16], uint64_
     }
 }
 
-// Tile geometry of the sv2 kernels as a function of the bytes a window needs (KM = K, or K + W - 1 for the fused minimizers): up to 32 bytes
-// reach at most into the lane before the previous one - lanes 0 / 1 are halo, a tile advances by 62 lanes; 33 .. 48 bytes (fused minimizers
-// such as (23, 11)) reach one lane further: three halo lanes, 61 emitting ones.
-template <int KM> struct Sv2Geom {
+// Tile geometry of the sv2 kernels as a function of the bytes a window needs (KM = K, or K + W - 1 for the fused minimizers).  With whole
+// halo lanes (EXACT = false: the fused-minimizer builds) up to 32 bytes reach at most into the lane before the previous one - lanes 0 / 1 are
+// halo, a tile advances by 62 lanes; 33 .. 48 bytes (fused minimizers such as (23, 11)) reach one lane further: three halo lanes, 61 emitting ones.
+//
+// The k-mer builds (EXACT: W = 0) re-read only what a window needs.  A tile loads 1024 bytes, and the windows that lie wholly inside
+// them are the ones ending at its bytes KM - 1 .. 1023: the tile advances by 1024 - (KM - 1) bytes, rounded down to a dword so that every load
+// stays dword aligned - 1004 bytes at k = 21 where whole halo lanes gave 992, 1.2 % fewer tiles per launch.
+//   * 17 <= KM <= 32: kStride = (1025 - KM) & ~3.  The rounding leaves kOverlap = 0 .. 3 windows that both a tile and its predecessor hold
+//     whole (they end at bytes KM - 1 .. KM - 2 + kOverlap of the later tile, all in lane 1): they belong to the earlier tile, and
+//     window_masks_ab clears them for the later one.  No lane is halo as a whole: lane 1 emits from byte KM - 17 + kOverlap on.
+//   * KM <= 16: a window never reaches past the previous lane - lane 0 is the halo, 63 lanes emit, 1008 bytes, loads stay 16-byte aligned.
+// Tile t loads the bytes [t kStride - kHaloBytes, + 1024) and emits exactly the windows ENDING in [t kStride, (t + 1) kStride): the host
+// planner (ntk_plan.hpp) and tests/emu need nothing but these two numbers.  kHaloBytes = 1024 - kStride is a multiple of 4, not of 16.
+template <int KM, bool EXACT = false> struct Sv2Geom {
     static_assert(KM >= 1 && KM <= 48, "window of at most 48 bytes");
-    static constexpr int kHalo = KM <= 32 ? 2 : 3;
+    static constexpr int kHalo = KM > 32 ? 3 : ((!EXACT || KM >= 17) ? 2 : 1);   // lanes that hold halo bytes
     static constexpr int kSlots = 64 - kHalo;
-#ifdef NTK_X_EXACTHALO   // kbench experiment (profiles/r06q): a tile advances by all the bytes whose windows lie inside it, 1024 - (k - 1) rounded down to a dword
-    static constexpr int kStride = (KM >= 17 && KM <= 32) ? ((1024 - (KM - 1)) & ~3) : kSlots * 16;
-#else
-    static constexpr int kStride = kSlots * 16;
-#endif
-    static constexpr int kHaloBytes = kHalo * 16;
-    static constexpr uint64_t kKeep = ~((1ull << kHalo) - 1ull);   // lanes that emit
+    static constexpr int kStride = sv2_stride_bytes(KM, EXACT);
+    static constexpr int kHaloBytes = kTileBytes - kStride;
+    static constexpr int kOverlap = (EXACT && KM >= 17 && KM <= 32) ? kHaloBytes - (KM - 1) : 0;  // windows at a tile's start that the previous tile emits
+    static constexpr uint64_t kKeep = ~((1ull << kHalo) - 1ull);   // whole halo lanes and KM <= 16: the lanes that emit
+    static_assert(kStride % 4 == 0 && kOverlap >= 0 && kOverlap <= 3 && kSlots * 16 <= kStride, "tile geometry");
 };
 
 // The same for a window length known only at RUN TIME, any L >= 1 (written for the generic fused minimizer kernel, L = k + w - 1 <= 79; that
@@ -886,13 +902,13 @@ NTK_HD void window_masks_span(const uint64_t (&G)[16], uint64_t (&A)[16], uint64
 #pragma unroll
     for (int j = 1; j < 16; j++) A[j] = A[j - 1] & G[j];
 }
-// OK[j] = A[j] & B[j] for any compile-time window length 1 .. 48 (Sv2Geom<KM> says which lanes are halo)
-template <int KM>
+// OK[j] = A[j] & B[j] for any compile-time window length 1 .. 48 in the tile geometry of Sv2Geom<KM, EXACT>
+template <int KM, bool EXACT = false>
 NTK_HD void window_masks_ab_any(const uint64_t (&G)[16], uint64_t (&A)[16], uint64_t (&B)[16])
 {
-    if constexpr (KM > 32) window_masks_span<(KM - 2) & 15>(G, A, B, (uint32_t)((KM - 2) >> 4), Sv2Geom<KM>::kKeep);
-    else if constexpr (KM >= 17) window_masks_ab<KM>(G, A, B);
-    else window_masks1_ab<KM>(G, A, B);
+    if constexpr (KM > 32) window_masks_span<(KM - 2) & 15>(G, A, B, (uint32_t)((KM - 2) >> 4), Sv2Geom<KM, false>::kKeep);
+    else if constexpr (KM >= 17) window_masks_ab<KM, EXACT>(G, A, B);
+    else window_masks1_ab<KM>(G, A, B, Sv2Geom<KM, EXACT>::kKeep);
 }
 NTK_HD void window_masks_runtime(const uint64_t (&G)[16], uint64_t (&A)[16], uint64_t (&B)[16], uint32_t L, uint64_t keep)
 {

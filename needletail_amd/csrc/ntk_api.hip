@@ -19,6 +19,7 @@
 
 #include "ntk_kernels.hpp"
 #include "ntk_plan.hpp"
+#include "ntk_compat_plan.hpp"
 
 using namespace ntk;
 
@@ -96,14 +97,39 @@ struct Scratch {
 
 }  // namespace
 
-// Everything one in-flight chunk of the batched compat face owns (ntk_canonical_kmers_batch / ntk_bit_kmers_batch).
+// What the device buffers of a CompatBank hold.  The banks serve every batched face in turn, so a slot has one name per role; the slots
+// and their sizes are shared.
+enum BankSlot {
+    kSlotBytes = 0,        // every face: the chunk's bytes as uploaded (packed with break bytes for the item arrays, as they lie otherwise)
+    kSlotValues = 1,       // bit path: a packed value per position
+    kSlotFlags = 1,        // item arrays, byte path: a flag byte per position
+    kSlotMinStrand = 1,    // minimizers: is_rc per record
+    kSlotValid = 2,        // items: the valid16 plane
+    kSlotMinBytes = 2,     // minimizers: m bytes per record
+    kSlotRc = 3,           // items: the rc16 plane
+    kSlotMinPos = 3,       // minimizers: window start per record
+    kSlotCompaction = 4,   // item arrays: block_items u32[nblocks] | block_off u64[nblocks] | total u64 | counts u64[nrec]
+    kSlotTotal = 4,        // planes: the chunk's item total
+    kSlotBest = 4,         // minimizers: the wave kernel's word, then the long records' `best`
+    kSlotOffsets = 5,      // every face: the chunk's nrec + 1 record offsets
+    kSlotDense = 6,        // item arrays: pos | value | flag of the items that leave
+    kSlotStartBits = 6,    // planes: the record-start bitmap
+    kBankSlots = 7
+};
+
+// Everything one in-flight chunk of the batched compat faces owns (run_banked).
 struct CompatBank {
-    void *h_stage = nullptr; size_t h_stage_bytes = 0;   // pinned: record starts + packed bytes
+    void *h_stage = nullptr; size_t h_stage_bytes = 0;   // pinned: record starts + packed bytes (item arrays)
     uint64_t *h_total = nullptr;                         // pinned: the chunk's item total
-    Scratch d[7];   // 0 packed bytes, 1 values (bit path) / flag bytes (byte path), 2 valid16, 3 rc16, 4 compaction scratch, 5 record starts, 6 dense outputs
-    hipEvent_t ev_total = nullptr, ev_scattered = nullptr, ev_done = nullptr;
-    uint64_t r0 = 0, nrec = 0, n = 0, n_words = 0, nblocks = 0;
-    size_t o_off = 0, o_total = 0, o_counts = 0;
+    Scratch d[kBankSlots];
+    template <class T> T *at(BankSlot s) const { return (T *)d[s].p; }
+    hipEvent_t ev_ready = nullptr;      // the chunk is uploaded (item arrays: and its item total is in h_total)
+    hipEvent_t ev_computed = nullptr;   // its kernels have run: the download may start
+    hipEvent_t ev_landed = nullptr;     // its download has landed: the bank is free again
+    uint64_t r0 = 0, nrec = 0, n = 0;   // the chunk: records [r0, r0 + nrec), n bytes on the device
+    uint64_t wbase = 0;                 // planes: its first plane word
+    uint64_t n_words = 0, nblocks = 0;  // item arrays: the compaction's geometry ...
+    size_t o_off = 0, o_total = 0, o_counts = 0;   // ... and where kSlotCompaction keeps what
     bool busy = false;   // its D2H may still be running
 };
 
@@ -127,16 +153,20 @@ struct ntk_ctx {
     uint32_t lower_idx = 0;
     // ntk_ctx_set_option (test / A-B support, per ctx: nothing in the dispatch reads the environment)
     uint64_t minimizer_chunk = (uint64_t)256 << 20;  // NTK_OPT_MINIMIZER_CHUNK_BYTES: bytes of input per two-pass minimizer pass
-    uint64_t compat_chunk = (uint64_t)16 << 20;      // NTK_OPT_COMPAT_CHUNK_BYTES: packed bytes per chunk of the batched compat faces
+    uint64_t compat_chunk = kCompatChunkBytes;      // NTK_OPT_COMPAT_CHUNK_BYTES: packed bytes per chunk of the batched compat faces
     uint32_t route_off = 0;                          // NTK_OPT_MINIMIZER_ROUTE: NTK_ROUTE_NO_* bits
     uint32_t pack_threads = 8;                       // NTK_OPT_COMPAT_PACK_THREADS
     uint64_t wait_poll_us = 50;                      // NTK_OPT_BATCH_WAIT_POLL_US (0: block in hipEventSynchronize)
     uint64_t gz_limit = 0, gz_window = 0, pipe_stats = 0;   // NTK_OPT_GZ_INMEM_LIMIT_BYTES / _STREAM_WINDOW_BYTES / NTK_OPT_PIPE_STATS: read by the producer (ntk_fastx_api.cpp) through ntk_ctx_get_option; 0 = its default
     uint64_t *d_part_scalars = nullptr;
     int part_blocks = 0;
-    uint16_t *d_lut = nullptr;  // [0]=normalize(false) [1]=normalize(true) [2]=strip [3]=complement, 256 each
+    uint16_t *d_lut = nullptr;  // four byte maps of 256 entries each, in the order of the accessors below
+    const uint16_t *lut_normalize() const { return d_lut; }
+    const uint16_t *lut_normalize_iupac() const { return d_lut + 256; }
+    const uint16_t *lut_strip() const { return d_lut + 512; }
+    const uint16_t *lut_complement() const { return d_lut + 768; }
     Scratch scratch[6];
-    CompatBank bank[3];        // the chunks the batched compat face keeps in flight (see compat_batch)
+    CompatBank bank[kCompatBanks];   // the chunks the batched compat faces keep in flight (see run_banked)
     void *h_pinned = nullptr;  // small pinned staging for scalar read-backs
     bool timing = false;
     std::vector<hipEvent_t> ev_free;
@@ -382,7 +412,7 @@ void launch_raw_bytes(ntk_ctx *c, bool wide, int blocks, const uint8_t *d_seq, u
 {
     const uint32_t pb = k < 6 ? k : 6;
     launch_with_quality(c, wide ? bytes_reduce_q<true> : bytes_reduce_q<false>, wide ? &canonical_bytes_reduce_kernel<true> : &canonical_bytes_reduce_kernel<false>,
-                        blocks, kPlThreads, d_qual, cutoff, d_seq, n, (n + 15) & ~(uint64_t)15, k, 2u * (k - pb), (const uint16_t *)(c->d_lut + 768),
+                        blocks, kPlThreads, d_qual, cutoff, d_seq, n, (n + 15) & ~(uint64_t)15, k, 2u * (k - pb), c->lut_complement(),
                         c->d_part_hist, c->d_part_scalars, run_if, wide && normalized ? 1u : 0u);
 }
 
@@ -714,7 +744,7 @@ void ntk_ctx_destroy(ntk_ctx *c)
         if (b.h_stage) (void)hipHostFree(b.h_stage);
         if (b.h_total) (void)hipHostFree(b.h_total);
         for (auto &s : b.d) if (s.p) (void)hipFree(s.p);
-        for (hipEvent_t e : {b.ev_total, b.ev_scattered, b.ev_done}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {b.ev_ready, b.ev_computed, b.ev_landed}) if (e) (void)hipEventDestroy(e);
     }
     if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -769,8 +799,8 @@ int ntk_ctx_set_option(ntk_ctx *c, int option, uint64_t value)
 {
     if (!c) return NTK_ERR_BAD_ARG;
     switch (option) {
-    case NTK_OPT_COMPAT_CHUNK_BYTES:      // 0 = default; below 64 bytes is taken as 64 (a stray 1 would cost a launch and an event wait per record)
-        c->compat_chunk = value == 0 ? ((uint64_t)16 << 20) : (value < 64 ? 64 : value);
+    case NTK_OPT_COMPAT_CHUNK_BYTES:      // 0 = default; below kCompatChunkMin is taken as that
+        c->compat_chunk = value == 0 ? kCompatChunkBytes : (value < kCompatChunkMin ? kCompatChunkMin : value);
         return NTK_OK;
     case NTK_OPT_MINIMIZER_CHUNK_BYTES:   // 0 = default; a multiple of 4096, at least 4096
         if (value && value < 4096) return NTK_ERR_BAD_ARG;
@@ -1151,7 +1181,7 @@ int ntk_normalize(ntk_ctx *c, const uint8_t *seq, uint64_t n, int allow_iupac, u
 {
     if (!c || (!seq && n) || (!out && n) || !out_len) return NTK_ERR_BAD_ARG;
     uint32_t flags[2];
-    int rc = compact_with_lut(c, seq, n, c->d_lut + (allow_iupac ? 256 : 0), out, out_len, flags);
+    int rc = compact_with_lut(c, seq, n, allow_iupac ? c->lut_normalize_iupac() : c->lut_normalize(), out, out_len, flags);
     if (rc) return rc;
     if (changed) *changed = flags[0] ? 1 : 0;
     return NTK_OK;
@@ -1161,7 +1191,7 @@ int ntk_strip_returns(ntk_ctx *c, const uint8_t *seq, uint64_t n, uint8_t *out, 
 {
     if (!c || (!seq && n) || (!out && n) || !out_len) return NTK_ERR_BAD_ARG;
     uint32_t flags[2];
-    int rc = compact_with_lut(c, seq, n, c->d_lut + 512, out, out_len, flags);
+    int rc = compact_with_lut(c, seq, n, c->lut_strip(), out, out_len, flags);
     if (rc) return rc;
     if (borrowed) *borrowed = flags[1] ? 0 : 1;
     return NTK_OK;
@@ -1178,7 +1208,7 @@ int ntk_reverse_complement(ntk_ctx *c, const uint8_t *seq, uint64_t n, uint8_t *
     uint8_t *d_in = (uint8_t *)c->scratch[0].p, *d_out = (uint8_t *)c->scratch[1].p;
     HIPCHK(hipMemcpyAsync(d_in, seq, n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(map_reverse_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream,
-                       (const uint8_t *)d_in, d_out, n, (const uint16_t *)(c->d_lut + 768));
+                       (const uint8_t *)d_in, d_out, n, c->lut_complement());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1204,19 +1234,6 @@ int ntk_bit_kmers(ntk_ctx *c, const uint8_t *seq, uint64_t n, uint32_t k, int ca
 
 /* ---- batched compat face ------------------------------------------------------------------------------------------- */
 namespace {
-// The items of Sequence::canonical_kmers / bit_kmers (reference src/sequence.rs:237-252) for a whole batch of records in ONE call.
-// The batch is cut into chunks of <= kCompatChunkBytes packed bytes that run through a two-deep pipeline, each chunk owning one
-// CompatBank (pinned staging + device buffers):
-//     A(c):  pack chunk c into pinned memory (one break byte after each record) -> H2D -> scan -> valid / is_rc planes ->
-//            count + scan of the items per 16 384-position block -> the chunk's item total to pinned memory        [ctx stream]
-//     B(c):  (total known) scatter into dense (pos, value, flag) arrays + per-record counts                        [ctx stream]
-//            -> D2H straight into the caller's arrays at the chunk's item offset                                   [copy stream]
-// and the host issues A(c+1) before B(c): while the copy engine drains chunk c's items (the 9 B per item going back over PCIe are
-// the bound of this face), the CPU packs chunk c+1 and the GPU scans it.  THREE banks rotate: a bank is free again when its
-// chunk's D2H has finished, and with two the host would wait for D2H(c-1) - enqueued a moment ago - before it could pack chunk
-// c+1 (measured: 3.85 ms per chunk = 2.35 ms of copies + 1.5 ms of packing in series, profiles/r03b/compat_trace.txt).
-// Caller arrays may be pageable or pinned (ntk_pinned_alloc).
-// (chunk size: ntk_ctx::compat_chunk, 16 MiB; NTK_OPT_COMPAT_CHUNK_BYTES lets the suites force many chunks out of small batches)
 // The banks keep their staging and device buffers between calls (re-allocation costs milliseconds); what a call leaves behind above
 // this many bytes per bank is released when it returns (a single 10-kb-record batch used to pin ~1.2 GiB until ctx_destroy).
 constexpr size_t kBankKeepBytes = (size_t)512 << 20;   // a 16 MiB chunk of the bit path needs ~420 MiB per bank: kept; more than that: released
@@ -1230,7 +1247,7 @@ void bank_trim(ntk_ctx *c, size_t keep = kBankKeepBytes)
     }
 }
 
-int bank_scratch(ntk_ctx *c, CompatBank &b, int slot, size_t bytes)
+int bank_scratch(ntk_ctx *c, CompatBank &b, BankSlot slot, size_t bytes)
 {
     if (bytes < 256) bytes = 256;
     Scratch &s = b.d[slot];
@@ -1243,17 +1260,67 @@ int bank_scratch(ntk_ctx *c, CompatBank &b, int slot, size_t bytes)
     return NTK_OK;
 }
 
-int bank_init(ntk_ctx *c, CompatBank &b)
+int bank_init(CompatBank &b)
 {
-    (void)c;
-    if (b.ev_total) return NTK_OK;
-    HIPCHK(hipEventCreateWithFlags(&b.ev_total, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&b.ev_scattered, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&b.ev_done, hipEventDisableTiming));
+    if (b.ev_ready) return NTK_OK;
+    HIPCHK(hipEventCreateWithFlags(&b.ev_ready, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&b.ev_computed, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&b.ev_landed, hipEventDisableTiming));
     HIPCHK(hipHostMalloc((void **)&b.h_total, 64, hipHostMallocDefault));
     return NTK_OK;
 }
 
+int stream_sync(hipStream_t s) { HIPCHK(hipStreamSynchronize(s)); return NTK_OK; }
+
+// The pipeline every batched Sequence-trait call runs on.  The batch is cut into chunks of <= ntk_ctx::compat_chunk bytes (compat_cut;
+// NTK_OPT_COMPAT_CHUNK_BYTES lets the suites force many chunks out of small batches) and chunk i owns bank i % kCompatBanks while it is
+// in flight.  A face supplies two bodies that only enqueue:
+//     in(bank, cut):  note the chunk in the bank, size the bank's buffers, upload, and whatever must precede the download
+//     out(bank):      what is left of the chunk's device work, the download into the caller's arrays, ev_landed recorded, busy = true
+// and the host issues in(i + 1) before out(i): while the copy engine drains chunk i, chunk i + 1 is staged and uploaded.  THREE banks
+// rotate: a bank is free again when its chunk's download has landed, and with two the host would wait for download(i - 1) - enqueued a
+// moment ago - before it could stage chunk i + 1 (measured on the item arrays: 3.85 ms per chunk = 2.35 ms of copies + 1.5 ms of packing
+// in series, profiles/r03b/compat_trace.txt).  retired(bank) runs once for every chunk whose download has landed.
+// The call is synchronous: everything of it has landed (or, after an error, nothing of it is still reading the pinned staging buffers or
+// writing the caller's arrays) when it returns.  The first failing stage's status wins over a failed synchronise.
+extern "C++" template <class In, class Out, class Retired>   // (this part of the file sits inside extern "C")
+int run_banked(ntk_ctx *c, const uint64_t *offsets, uint64_t n_records, uint64_t per_record, bool downloads_on_down_stream, In in, Out out,
+               Retired retired)
+{
+    int rc = NTK_OK;
+    for (CompatBank &b : c->bank) if ((rc = bank_init(b))) return rc;
+    auto retire = [&](CompatBank &b) -> int {
+        if (!b.busy) return NTK_OK;
+        HIPCHK(hipEventSynchronize(b.ev_landed));
+        b.busy = false;
+        retired(b);
+        return NTK_OK;
+    };
+    CompatBank *prev = nullptr;
+    uint64_t ci = 0;
+    for (uint64_t r0 = 0; r0 < n_records; ci++) {
+        const CompatCut cut = compat_cut(offsets, n_records, r0, c->compat_chunk, per_record);
+        CompatBank &b = c->bank[ci % kCompatBanks];
+        if ((rc = retire(b)) || (rc = in(b, cut)) || (prev && (rc = out(*prev)))) break;
+        prev = &b; r0 = cut.r1;
+    }
+    if (rc == NTK_OK && prev) rc = out(*prev);
+    const int down = downloads_on_down_stream ? stream_sync(c->down_stream) : NTK_OK, compute = stream_sync(c->stream), copy = stream_sync(c->copy_stream);
+    if (rc == NTK_OK) rc = down ? down : compute ? compute : copy;
+    // (the streams are idle: what was still in flight has landed, no event needs waiting for)
+    for (CompatBank &b : c->bank) { if (rc == NTK_OK && b.busy) retired(b); b.busy = false; }
+    bank_trim(c);
+    return rc;
+}
+
+// ---- item arrays -------------------------------------------------------------------------------------------------------------------
+// The items of Sequence::canonical_kmers / bit_kmers (reference src/sequence.rs:237-252) for a whole batch of records in ONE call:
+//     in:   pack the chunk into pinned memory (one break byte after each record) -> H2D -> scan -> valid / is_rc planes ->
+//           count + scan of the items per 16 384-position block -> the chunk's item total to pinned memory            [ctx stream]
+//     out:  (total known) scatter into dense (pos, value, flag) arrays + per-record counts                            [ctx stream]
+//           -> D2H straight into the caller's arrays at the chunk's item offset                                       [copy stream]
+// While the copy engine drains chunk i's items (the 9 B per item going back over PCIe are the bound of this face), the CPU packs chunk
+// i + 1 and the GPU scans it.  Caller arrays may be pageable or pinned (ntk_pinned_alloc).
 struct CompatJob {
     const uint8_t *seq; const uint64_t *offsets;
     uint32_t k; int kind;   // 0: byte path (raw-byte CanonicalKmers, any k <= 255), 1: bit path canonical, 2: bit path forward
@@ -1261,11 +1328,11 @@ struct CompatJob {
     uint64_t cap;
 };
 
-// A: records [r0, r0 + nrec) of the job into bank b, up to the item total
-int compat_stage_a(ntk_ctx *c, CompatBank &b, const CompatJob &j, uint64_t r0, uint64_t nrec)
+// in: the records of the cut into bank b, up to the item total
+int compat_stage_a(ntk_ctx *c, CompatBank &b, const CompatJob &j, const CompatCut &cut)
 {
     int rc;
-    const uint64_t n = j.offsets[r0 + nrec] - j.offsets[r0] + nrec;
+    const uint64_t r0 = cut.r0, nrec = cut.nrec(), n = cut.bytes;
     const size_t stage_bytes = (size_t)n + (size_t)(nrec + 1) * 8 + 64;
     if (b.h_stage_bytes < stage_bytes) {
         if (b.h_stage) { HIPCHK(hipHostFree(b.h_stage)); b.h_stage = nullptr; b.h_stage_bytes = 0; }
@@ -1308,67 +1375,65 @@ int compat_stage_a(ntk_ctx *c, CompatBank &b, const CompatJob &j, uint64_t r0, u
     h_start[nrec] = n;
     b.r0 = r0; b.nrec = nrec; b.n = n;
     const uint64_t nt = (n + 15) / 16 * 16;
-    if ((rc = bank_scratch(c, b, 0, nt + 16))) return rc;
-    if ((rc = bank_scratch(c, b, 5, (size_t)(nrec + 1) * 8))) return rc;
-    if ((rc = bank_scratch(c, b, 1, j.kind == 0 ? nt : nt * 8))) return rc;
-    if ((rc = bank_scratch(c, b, 2, nt / 8 + 16))) return rc;
-    if ((rc = bank_scratch(c, b, 3, nt / 8 + 16))) return rc;
+    if ((rc = bank_scratch(c, b, kSlotBytes, nt + 16))) return rc;
+    if ((rc = bank_scratch(c, b, kSlotOffsets, (size_t)(nrec + 1) * 8))) return rc;
+    if ((rc = bank_scratch(c, b, j.kind == 0 ? kSlotFlags : kSlotValues, j.kind == 0 ? nt : nt * 8))) return rc;
+    if ((rc = bank_scratch(c, b, kSlotValid, nt / 8 + 16))) return rc;
+    if ((rc = bank_scratch(c, b, kSlotRc, nt / 8 + 16))) return rc;
     b.n_words = (n + 15) >> 4;
     b.nblocks = (b.n_words + kCpBlockWords - 1) / kCpBlockWords;
-    // one slot holds: block_items u32[nblocks] | block_off u64[nblocks] | total u64 | counts u64[nrec]
     b.o_off = ((size_t)b.nblocks * 4 + 7) & ~(size_t)7; b.o_total = b.o_off + (size_t)b.nblocks * 8; b.o_counts = b.o_total + 8;
-    if ((rc = bank_scratch(c, b, 4, b.o_counts + (size_t)nrec * 8))) return rc;
-    HIPCHK(hipMemcpyAsync(b.d[0].p, h_seq, n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b.d[5].p, h_start, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    uint16_t *d_v16 = (uint16_t *)b.d[2].p, *d_r16 = (uint16_t *)b.d[3].p;
+    if ((rc = bank_scratch(c, b, kSlotCompaction, b.o_counts + (size_t)nrec * 8))) return rc;
+    const uint8_t *d_bytes = b.at<uint8_t>(kSlotBytes);
+    HIPCHK(hipMemcpyAsync(b.at<uint8_t>(kSlotBytes), h_seq, n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b.at<uint64_t>(kSlotOffsets), h_start, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    uint16_t *d_v16 = b.at<uint16_t>(kSlotValid), *d_r16 = b.at<uint16_t>(kSlotRc);
     if (j.kind == 0) {
         // raw-byte comparison exactly as the reference (src/kmer.rs:84-129): any k <= 255, mixed case compares as bytes
-        uint8_t *d_flags = (uint8_t *)b.d[1].p;
+        uint8_t *d_flags = b.at<uint8_t>(kSlotFlags);
         hipLaunchKernelGGL(canonical_bytes_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream,
-                           (const uint8_t *)b.d[0].p, n, j.k, (const uint16_t *)(c->d_lut + 768), d_flags, (const uint32_t *)nullptr);
+                           d_bytes, n, j.k, c->lut_complement(), d_flags, (const uint32_t *)nullptr);
         hipLaunchKernelGGL(pack_flags8_kernel, dim3(grid_for((n + 15) / 16, 256)), dim3(256), 0, c->stream, (const uint8_t *)d_flags, n, d_v16, d_r16);
         HIPCHK(hipGetLastError());
     } else {
-        ntk_params p = {j.k, (uint32_t)(j.kind == 1 ? NTK_PATH_BITS_CANONICAL : NTK_PATH_BITS), NTK_PRE_NONE, 0};
-        Mode m;
-        if ((rc = resolve_mode(&p, true, &m))) return rc;
-        if ((rc = run_scan(c, (const uint8_t *)b.d[0].p, n, &p, m, false, (uint64_t *)b.d[1].p, d_v16, d_r16))) return rc;
+        const ntk_params p = {j.k, (uint32_t)(j.kind == 1 ? NTK_PATH_BITS_CANONICAL : NTK_PATH_BITS), NTK_PRE_NONE, 0};
+        if ((rc = ntk_materialize_device(c, d_bytes, n, &p, b.at<uint64_t>(kSlotValues), d_v16, d_r16))) return rc;
     }
-    uint8_t *base = (uint8_t *)b.d[4].p;
+    uint8_t *base = b.at<uint8_t>(kSlotCompaction);
     hipLaunchKernelGGL(cp_count_kernel, dim3((unsigned)b.nblocks), dim3(kCpThreads), 0, c->stream, d_v16, b.n_words, (uint32_t *)base);
     hipLaunchKernelGGL(cp_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t *)base, (uint64_t *)(base + b.o_off), b.nblocks,
                        (uint64_t *)(base + b.o_total));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(b.h_total, base + b.o_total, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipEventRecord(b.ev_total, c->stream));
+    HIPCHK(hipEventRecord(b.ev_ready, c->stream));
     return NTK_OK;
 }
 
-// B: the chunk's items leave for the caller's arrays at item offset *base (capacity permitting); *base += the chunk's item total
+// out: the chunk's items leave for the caller's arrays at item offset *base (capacity permitting); *base += the chunk's item total
 int compat_stage_b(ntk_ctx *c, CompatBank &b, const CompatJob &j, uint64_t *base_items)
 {
     int rc;
-    HIPCHK(hipEventSynchronize(b.ev_total));
+    HIPCHK(hipEventSynchronize(b.ev_ready));
     const uint64_t m = *b.h_total, at = *base_items;
     const uint64_t take = at >= j.cap ? 0 : (m < j.cap - at ? m : j.cap - at);
     const bool values = j.kind != 0;
-    if ((rc = bank_scratch(c, b, 6, (size_t)take * (8 + (values ? 8 : 0) + 1) + 64))) return rc;
-    uint64_t *d_pos = (uint64_t *)b.d[6].p, *d_val = values ? d_pos + take : nullptr;
+    if ((rc = bank_scratch(c, b, kSlotDense, (size_t)take * (8 + (values ? 8 : 0) + 1) + 64))) return rc;
+    uint64_t *d_pos = b.at<uint64_t>(kSlotDense), *d_val = values ? d_pos + take : nullptr;
     uint8_t *d_flag = (uint8_t *)(d_pos + take + (values ? take : 0));
-    uint8_t *sb = (uint8_t *)b.d[4].p;
+    uint8_t *sb = b.at<uint8_t>(kSlotCompaction);
     uint64_t *d_counts = (uint64_t *)(sb + b.o_counts);
     HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)b.nrec * 8, c->stream));
-    hipLaunchKernelGGL(cp_scatter_kernel, dim3((unsigned)b.nblocks), dim3(kCpThreads), 0, c->stream, (const uint16_t *)b.d[2].p, (const uint16_t *)b.d[3].p,
-                       values ? (const uint64_t *)b.d[1].p : nullptr, b.n_words, (const uint64_t *)(sb + b.o_off), (const uint64_t *)b.d[5].p, b.nrec,
+    hipLaunchKernelGGL(cp_scatter_kernel, dim3((unsigned)b.nblocks), dim3(kCpThreads), 0, c->stream, b.at<const uint16_t>(kSlotValid), b.at<const uint16_t>(kSlotRc),
+                       values ? b.at<const uint64_t>(kSlotValues) : nullptr, b.n_words, (const uint64_t *)(sb + b.o_off), b.at<const uint64_t>(kSlotOffsets), b.nrec,
                        j.kind == 0 ? 0u : j.k - 1, take, d_pos, d_val, d_flag, (unsigned long long *)d_counts);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(b.ev_scattered, c->stream));
-    HIPCHK(hipStreamWaitEvent(c->copy_stream, b.ev_scattered, 0));
+    HIPCHK(hipEventRecord(b.ev_computed, c->stream));
+    HIPCHK(hipStreamWaitEvent(c->copy_stream, b.ev_computed, 0));
     if (j.counts) HIPCHK(hipMemcpyAsync(j.counts + b.r0, d_counts, (size_t)b.nrec * 8, hipMemcpyDeviceToHost, c->copy_stream));
     if (take && j.pos_out) HIPCHK(hipMemcpyAsync(j.pos_out + at, d_pos, (size_t)take * 8, hipMemcpyDeviceToHost, c->copy_stream));
     if (take && j.val_out && d_val) HIPCHK(hipMemcpyAsync(j.val_out + at, d_val, (size_t)take * 8, hipMemcpyDeviceToHost, c->copy_stream));
     if (take && j.flag_out) HIPCHK(hipMemcpyAsync(j.flag_out + at, d_flag, (size_t)take, hipMemcpyDeviceToHost, c->copy_stream));
-    HIPCHK(hipEventRecord(b.ev_done, c->copy_stream));
+    HIPCHK(hipEventRecord(b.ev_landed, c->copy_stream));
     b.busy = true;
     *base_items = at + m;
     return NTK_OK;
@@ -1377,30 +1442,11 @@ int compat_stage_b(ntk_ctx *c, CompatBank &b, const CompatJob &j, uint64_t *base
 int compat_batch(ntk_ctx *c, const CompatJob &j, uint64_t n_records, uint64_t *total)
 {
     for (uint64_t r = 0; r < n_records; r++) if (j.offsets[r] > j.offsets[r + 1]) return NTK_ERR_BAD_ARG;
-    int rc = NTK_OK;
-    for (CompatBank &b : c->bank) if ((rc = bank_init(c, b))) return rc;
-    uint64_t items = 0, r0 = 0;
-    int cur = 0, prev = -1;
-    const uint64_t chunk_bytes = c->compat_chunk;
-    constexpr int kBanks = (int)(sizeof(c->bank) / sizeof(c->bank[0]));
-    while (r0 < n_records && rc == NTK_OK) {
-        // the chunk: records up to chunk_bytes packed bytes (at least one record)
-        uint64_t r1 = r0 + 1;
-        while (r1 < n_records && j.offsets[r1 + 1] - j.offsets[r0] + (r1 + 1 - r0) <= chunk_bytes) r1++;
-        CompatBank &b = c->bank[cur];
-        if (b.busy) { if (hipEventSynchronize(b.ev_done) != hipSuccess) { g_last_hip = (int)hipGetLastError(); rc = NTK_ERR_HIP; break; } b.busy = false; }
-        if ((rc = compat_stage_a(c, b, j, r0, r1 - r0))) break;
-        if (prev >= 0 && (rc = compat_stage_b(c, c->bank[prev], j, &items))) break;
-        prev = cur; cur = (cur + 1) % kBanks; r0 = r1;
-    }
-    if (rc == NTK_OK && prev >= 0) rc = compat_stage_b(c, c->bank[prev], j, &items);
-    // the call is synchronous: everything of it has landed (or, after an error, nothing of it is still reading the pinned
-    // staging buffers or writing the caller's arrays) when it returns
-    const hipError_t e1 = hipStreamSynchronize(c->stream), e2 = hipStreamSynchronize(c->copy_stream);
-    for (CompatBank &b : c->bank) b.busy = false;
-    bank_trim(c);
+    uint64_t items = 0;
+    const int rc = run_banked(c, j.offsets, n_records, 1, false,
+                              [&](CompatBank &b, const CompatCut &cut) { return compat_stage_a(c, b, j, cut); },
+                              [&](CompatBank &b) { return compat_stage_b(c, b, j, &items); }, [](CompatBank &) {});
     if (rc != NTK_OK) return rc;
-    if (e1 != hipSuccess || e2 != hipSuccess) { g_last_hip = (int)(e1 != hipSuccess ? e1 : e2); return NTK_ERR_HIP; }
     *total = items;
     return items > j.cap ? NTK_ERR_CAPACITY : NTK_OK;
 }
@@ -1410,9 +1456,10 @@ int compat_batch(ntk_ctx *c, const CompatJob &j, uint64_t n_records, uint64_t *t
 // so all the device has to return is, per window start, "emitted?" and "is_rc?": TWO BITS per sequence byte instead of nine bytes per
 // item (the bound of ntk_canonical_kmers_batch: 48 GB/s of items over PCIe = 6.3 Gbases/s).  The caller's bytes are uploaded as they
 // lie (no packing pass, no break bytes: record starts travel as a bitmap built on the device from the offsets), the raw-byte kernel
-// of the compat face marks the windows, and the two planes come back: 1/4 byte per input byte.  Chunks of <= 16 MiB, the same three
-// banks: upload and kernels of chunk i + 1 overlap the download of chunk i.  Each chunk starts on a 16-position word boundary of the
-// planes; rec_bit[r] is the plane position of record r's first byte.
+// of the compat face marks the windows, and the two planes come back: 1/4 byte per input byte.  Three stages per chunk on three streams:
+// in = upload [copy stream]; out = bitmap + planes kernel [ctx stream] -> download [down stream].  The uploads run back to back (the call
+// is bound by them); the kernel and the download of chunk i hide behind the upload of chunk i + 1.  Each chunk starts on a 16-position
+// word boundary of the planes; rec_bit[r] is the plane position of record r's first byte.
 // kind 0: the byte path (CanonicalKmers, raw-byte compare, any k <= 255); 1 / 2: the bit path, canonical / forward-only (BitNuclKmer, k <= 32),
 // with values != nullptr also the items' packed values, one u64 per plane position (0 where nothing is emitted): 8 more bytes per input byte
 // come back then, and the download is the call's bound.
@@ -1420,199 +1467,128 @@ int compat_planes(ntk_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint6
                   uint16_t *valid16, uint16_t *rc16, uint64_t cap_words, uint64_t *n_words, uint64_t *total, int kind = 0, uint64_t *values = nullptr)
 {
     for (uint64_t r = 0; r < n_records; r++) if (offsets[r] > offsets[r + 1]) return NTK_ERR_BAD_ARG;
-    const uint64_t chunk_bytes = c->compat_chunk;
-    constexpr int kBanks = (int)(sizeof(c->bank) / sizeof(c->bank[0]));
-    // pass 1 (host): the chunks and the words they need
-    struct Chunk { uint64_t r0, r1, wbase, nb; };
-    std::vector<Chunk> chunks;
+    // pass 1 (host): the words the chunks need
     uint64_t words = 0;
-    try {
-        for (uint64_t r0 = 0; r0 < n_records;) {
-            uint64_t r1 = r0 + 1;
-            while (r1 < n_records && offsets[r1 + 1] - offsets[r0] <= chunk_bytes) r1++;
-            const uint64_t nb = offsets[r1] - offsets[r0];
-            chunks.push_back({r0, r1, words, nb});
-            words += (nb + 15) >> 4;
-            r0 = r1;
-        }
-    } catch (...) { return NTK_ERR_NOMEM; }
+    for (uint64_t r0 = 0; r0 < n_records;) {
+        const CompatCut cut = compat_cut(offsets, n_records, r0, c->compat_chunk, 0);
+        words += (cut.bytes + 15) >> 4;
+        r0 = cut.r1;
+    }
     *n_words = words;
     if (words > cap_words) return NTK_ERR_CAPACITY;
-    int rc = NTK_OK;
-    for (CompatBank &b : c->bank) if ((rc = bank_init(c, b))) return rc;
-    uint64_t items = 0;
-    auto retire = [&](CompatBank &b) -> int {   // the bank's chunk has fully landed: its item total joins the sum
-        if (!b.busy) return NTK_OK;
-        if (hipEventSynchronize(b.ev_done) != hipSuccess) { g_last_hip = (int)hipGetLastError(); return NTK_ERR_HIP; }
-        items += *b.h_total;
-        b.busy = false;
-        return NTK_OK;
-    };
-    // Three stages per chunk on three streams: upload [copy stream] -> bitmap + planes kernel [ctx stream] -> download [down stream]:
-    // the uploads run back to back (the call is bound by them), the kernel and the download of chunk i hide behind the upload of
-    // chunk i + 1.  A bank is re-used every third chunk, after its download has landed (retire()).
-    auto hip_fail = [&](hipError_t e) { g_last_hip = (int)e; return NTK_ERR_HIP; };
-    auto upload = [&](size_t ci) -> int {
-        const Chunk &ch = chunks[ci];
-        CompatBank &b = c->bank[ci % kBanks];
+    uint64_t items = 0, wbase = 0;
+    auto upload = [&](CompatBank &b, const CompatCut &cut) -> int {
+        const uint64_t nrec = cut.nrec(), nt = (cut.bytes + 15) / 16 * 16;
+        b.r0 = cut.r0; b.nrec = nrec; b.n = cut.bytes; b.wbase = wbase;
+        wbase += nt >> 4;
+        for (uint64_t q = cut.r0; q < cut.r1; q++) rec_bit[q] = b.wbase * 16 + (offsets[q] - offsets[cut.r0]);
+        if (b.n == 0) return NTK_OK;   // only empty records
         int r;
-        if ((r = retire(b))) return r;
-        const uint64_t nrec = ch.r1 - ch.r0, nt = (ch.nb + 15) / 16 * 16;
-        for (uint64_t q = ch.r0; q < ch.r1; q++) rec_bit[q] = ch.wbase * 16 + (offsets[q] - offsets[ch.r0]);
-        if (ch.nb == 0) return NTK_OK;   // only empty records
-        if ((r = bank_scratch(c, b, 0, nt + 16))) return r;
-        if ((r = bank_scratch(c, b, 5, (size_t)(nrec + 1) * 8))) return r;
-        if ((r = bank_scratch(c, b, 2, nt / 8 + 16))) return r;
-        if ((r = bank_scratch(c, b, 3, nt / 8 + 16))) return r;
-        if ((r = bank_scratch(c, b, 4, 64))) return r;
-        if ((r = bank_scratch(c, b, 6, (size_t)((nt >> 5) + 2) * 4))) return r;
-        if (values && (r = bank_scratch(c, b, 1, (size_t)nt * 8))) return r;
-        hipError_t e;
-        if ((e = hipMemcpyAsync(b.d[0].p, seq + offsets[ch.r0], ch.nb, hipMemcpyHostToDevice, c->copy_stream))) return hip_fail(e);
-        if ((e = hipMemcpyAsync(b.d[5].p, offsets + ch.r0, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, c->copy_stream))) return hip_fail(e);
-        if ((e = hipEventRecord(b.ev_total, c->copy_stream))) return hip_fail(e);   // "uploaded"
+        if ((r = bank_scratch(c, b, kSlotBytes, nt + 16))) return r;
+        if ((r = bank_scratch(c, b, kSlotOffsets, (size_t)(nrec + 1) * 8))) return r;
+        if ((r = bank_scratch(c, b, kSlotValid, nt / 8 + 16))) return r;
+        if ((r = bank_scratch(c, b, kSlotRc, nt / 8 + 16))) return r;
+        if ((r = bank_scratch(c, b, kSlotTotal, 64))) return r;
+        if ((r = bank_scratch(c, b, kSlotStartBits, (size_t)((nt >> 5) + 2) * 4))) return r;
+        if (values && (r = bank_scratch(c, b, kSlotValues, (size_t)nt * 8))) return r;
+        HIPCHK(hipMemcpyAsync(b.at<uint8_t>(kSlotBytes), seq + offsets[b.r0], b.n, hipMemcpyHostToDevice, c->copy_stream));
+        HIPCHK(hipMemcpyAsync(b.at<uint64_t>(kSlotOffsets), offsets + b.r0, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, c->copy_stream));
+        HIPCHK(hipEventRecord(b.ev_ready, c->copy_stream));
         return NTK_OK;
     };
-    auto compute_and_download = [&](size_t ci) -> int {
-        const Chunk &ch = chunks[ci];
-        CompatBank &b = c->bank[ci % kBanks];
-        if (ch.nb == 0) return NTK_OK;
-        const uint64_t nrec = ch.r1 - ch.r0, nb = ch.nb, nt = (nb + 15) / 16 * 16, nw = nt >> 4, sb_words = (nt >> 5) + 2;
-        hipError_t e;
-        if ((e = hipStreamWaitEvent(c->stream, b.ev_total, 0))) return hip_fail(e);
-        if ((e = hipMemsetAsync(b.d[6].p, 0, (size_t)sb_words * 4, c->stream))) return hip_fail(e);
-        if ((e = hipMemsetAsync(b.d[4].p, 0, 8, c->stream))) return hip_fail(e);
-        hipLaunchKernelGGL(mark_record_starts_kernel, dim3(grid_for(nrec, 256)), dim3(256), 0, c->stream, (const uint64_t *)b.d[5].p, nrec, nb,
-                           (uint32_t *)b.d[6].p);
+    auto compute_and_download = [&](CompatBank &b) -> int {
+        if (b.n == 0) return NTK_OK;
+        const uint64_t nrec = b.nrec, nb = b.n, nt = (nb + 15) / 16 * 16, nw = nt >> 4, sb_words = (nt >> 5) + 2;
+        const uint8_t *d_bytes = b.at<uint8_t>(kSlotBytes);
+        uint32_t *d_starts = b.at<uint32_t>(kSlotStartBits);
+        uint16_t *d_v16 = b.at<uint16_t>(kSlotValid), *d_r16 = b.at<uint16_t>(kSlotRc);
+        uint64_t *d_values = values ? b.at<uint64_t>(kSlotValues) : nullptr;
+        unsigned long long *d_total = b.at<unsigned long long>(kSlotTotal);
+        HIPCHK(hipStreamWaitEvent(c->stream, b.ev_ready, 0));
+        HIPCHK(hipMemsetAsync(d_starts, 0, (size_t)sb_words * 4, c->stream));
+        HIPCHK(hipMemsetAsync(d_total, 0, 8, c->stream));
+        hipLaunchKernelGGL(mark_record_starts_kernel, dim3(grid_for(nrec, 256)), dim3(256), 0, c->stream, b.at<const uint64_t>(kSlotOffsets), nrec, nb, d_starts);
         const uint64_t tiles = (nb + kPlTile - 1) / kPlTile;
         const dim3 grid((unsigned)(tiles < (uint64_t)c->n_cu * 8 ? tiles : (uint64_t)c->n_cu * 8));
         if (kind == 0)
-            hipLaunchKernelGGL(canonical_bytes_planes_kernel, grid, dim3(kPlThreads), 0, c->stream, (const uint8_t *)b.d[0].p, nb, nt + 16, k,
-                               (const uint16_t *)(c->d_lut + 768), (const uint32_t *)b.d[6].p, sb_words, (uint16_t *)b.d[2].p, (uint16_t *)b.d[3].p,
-                               (unsigned long long *)b.d[4].p);
+            hipLaunchKernelGGL(canonical_bytes_planes_kernel, grid, dim3(kPlThreads), 0, c->stream, d_bytes, nb, nt + 16, k, c->lut_complement(),
+                               (const uint32_t *)d_starts, sb_words, d_v16, d_r16, d_total);
         else if (kind == 1)
-            hipLaunchKernelGGL(bit_kmers_planes_kernel<true>, grid, dim3(kPlThreads), 0, c->stream, (const uint8_t *)b.d[0].p, nb, nt + 16, k,
-                               (const uint32_t *)b.d[6].p, sb_words, (uint16_t *)b.d[2].p, (uint16_t *)b.d[3].p, values ? (uint64_t *)b.d[1].p : nullptr,
-                               (unsigned long long *)b.d[4].p);
+            hipLaunchKernelGGL(bit_kmers_planes_kernel<true>, grid, dim3(kPlThreads), 0, c->stream, d_bytes, nb, nt + 16, k,
+                               (const uint32_t *)d_starts, sb_words, d_v16, d_r16, d_values, d_total);
         else
-            hipLaunchKernelGGL(bit_kmers_planes_kernel<false>, grid, dim3(kPlThreads), 0, c->stream, (const uint8_t *)b.d[0].p, nb, nt + 16, k,
-                               (const uint32_t *)b.d[6].p, sb_words, (uint16_t *)b.d[2].p, (uint16_t *)b.d[3].p, values ? (uint64_t *)b.d[1].p : nullptr,
-                               (unsigned long long *)b.d[4].p);
-        if ((e = hipGetLastError())) return hip_fail(e);
-        if ((e = hipMemcpyAsync(b.h_total, b.d[4].p, 8, hipMemcpyDeviceToHost, c->stream))) return hip_fail(e);
-        if ((e = hipEventRecord(b.ev_scattered, c->stream))) return hip_fail(e);
-        if ((e = hipStreamWaitEvent(c->down_stream, b.ev_scattered, 0))) return hip_fail(e);
-        if ((e = hipMemcpyAsync(valid16 + ch.wbase, b.d[2].p, (size_t)nw * 2, hipMemcpyDeviceToHost, c->down_stream))) return hip_fail(e);
-        if ((e = hipMemcpyAsync(rc16 + ch.wbase, b.d[3].p, (size_t)nw * 2, hipMemcpyDeviceToHost, c->down_stream))) return hip_fail(e);
-        if (values && (e = hipMemcpyAsync(values + ch.wbase * 16, b.d[1].p, (size_t)nw * 16 * 8, hipMemcpyDeviceToHost, c->down_stream))) return hip_fail(e);
-        if ((e = hipEventRecord(b.ev_done, c->down_stream))) return hip_fail(e);
+            hipLaunchKernelGGL(bit_kmers_planes_kernel<false>, grid, dim3(kPlThreads), 0, c->stream, d_bytes, nb, nt + 16, k,
+                               (const uint32_t *)d_starts, sb_words, d_v16, d_r16, d_values, d_total);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(b.h_total, d_total, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipEventRecord(b.ev_computed, c->stream));
+        HIPCHK(hipStreamWaitEvent(c->down_stream, b.ev_computed, 0));
+        HIPCHK(hipMemcpyAsync(valid16 + b.wbase, d_v16, (size_t)nw * 2, hipMemcpyDeviceToHost, c->down_stream));
+        HIPCHK(hipMemcpyAsync(rc16 + b.wbase, d_r16, (size_t)nw * 2, hipMemcpyDeviceToHost, c->down_stream));
+        if (values) HIPCHK(hipMemcpyAsync(values + b.wbase * 16, d_values, (size_t)nw * 16 * 8, hipMemcpyDeviceToHost, c->down_stream));
+        HIPCHK(hipEventRecord(b.ev_landed, c->down_stream));
         b.busy = true;
         return NTK_OK;
     };
-    if (!chunks.empty()) rc = upload(0);
-    for (size_t ci = 0; ci < chunks.size() && rc == NTK_OK; ci++) {
-        if (ci + 1 < chunks.size() && (rc = upload(ci + 1))) break;
-        rc = compute_and_download(ci);
-    }
+    // a chunk that has fully landed: its item total joins the sum
+    const int rc = run_banked(c, offsets, n_records, 0, true, upload, compute_and_download, [&](CompatBank &b) { items += *b.h_total; });
     rec_bit[n_records] = words * 16;
-    const hipError_t e0 = hipStreamSynchronize(c->down_stream);
-    const hipError_t e1 = e0 != hipSuccess ? e0 : hipStreamSynchronize(c->stream), e2 = hipStreamSynchronize(c->copy_stream);
-    if (rc == NTK_OK) for (CompatBank &b : c->bank) if ((rc = retire(b))) break;
-    for (CompatBank &b : c->bank) b.busy = false;
-    bank_trim(c);
     if (rc != NTK_OK) return rc;
-    if (e1 != hipSuccess || e2 != hipSuccess) { g_last_hip = (int)(e1 != hipSuccess ? e1 : e2); return NTK_ERR_HIP; }
     *total = items;
     return NTK_OK;
 }
-// sequence::minimizer per record (ntk_minimizer_batch): the same three stages on three streams and three banks as compat_planes - upload
-// [copy stream] -> wave-per-record kernel [ctx stream] -> download of the chunk's minimizers / window starts / strands [down stream].
+
+// sequence::minimizer per record (ntk_minimizer_batch): the same three stages on three streams as compat_planes - upload [copy stream]
+// -> wave-per-record kernel [ctx stream] -> download of the chunk's minimizers / window starts / strands [down stream].
 int minimizer_batch_impl(ntk_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint64_t n_records, uint32_t m, uint8_t *out, uint64_t *pos_out,
                          uint8_t *is_rc_out)
 {
-    constexpr uint64_t kLongRecord = 1ull << 16;
-    constexpr int kBanks = (int)(sizeof(c->bank) / sizeof(c->bank[0]));
-    const uint64_t chunk_bytes = c->compat_chunk;
-    struct Chunk { uint64_t r0, r1, nb; };
-    std::vector<Chunk> chunks;
-    try {
-        for (uint64_t r0 = 0; r0 < n_records;) {
-            uint64_t r1 = r0 + 1;
-            while (r1 < n_records && offsets[r1 + 1] - offsets[r0] <= chunk_bytes) r1++;
-            chunks.push_back({r0, r1, offsets[r1] - offsets[r0]});
-            r0 = r1;
-        }
-    } catch (...) { return NTK_ERR_NOMEM; }
-    int rc = NTK_OK;
-    for (CompatBank &b : c->bank) if ((rc = bank_init(c, b))) return rc;
-    const uint16_t *comp = (const uint16_t *)(c->d_lut + 768);
-    auto hip_fail = [&](hipError_t e) { g_last_hip = (int)e; return NTK_ERR_HIP; };
-    auto retire = [&](CompatBank &b) -> int {
-        if (!b.busy) return NTK_OK;
-        if (hipEventSynchronize(b.ev_done) != hipSuccess) { g_last_hip = (int)hipGetLastError(); return NTK_ERR_HIP; }
-        b.busy = false;
-        return NTK_OK;
-    };
-    auto upload = [&](size_t ci) -> int {
-        const Chunk &ch = chunks[ci];
-        CompatBank &b = c->bank[ci % kBanks];
-        const uint64_t nrec = ch.r1 - ch.r0;
+    const uint16_t *comp = c->lut_complement();
+    auto upload = [&](CompatBank &b, const CompatCut &cut) -> int {
+        const uint64_t nrec = cut.nrec();
+        b.r0 = cut.r0; b.nrec = nrec; b.n = cut.bytes;
         int r;
-        if ((r = retire(b))) return r;
-        if ((r = bank_scratch(c, b, 0, ch.nb + 16))) return r;
-        if ((r = bank_scratch(c, b, 5, (size_t)(nrec + 1) * 8))) return r;
-        if ((r = bank_scratch(c, b, 2, (size_t)nrec * m))) return r;
-        if ((r = bank_scratch(c, b, 3, (size_t)nrec * 8))) return r;
-        if ((r = bank_scratch(c, b, 1, (size_t)nrec))) return r;
-        if ((r = bank_scratch(c, b, 4, 64))) return r;
-        hipError_t e;
-        if ((e = hipMemcpyAsync(b.d[0].p, seq + offsets[ch.r0], ch.nb, hipMemcpyHostToDevice, c->copy_stream))) return hip_fail(e);
-        if ((e = hipMemcpyAsync(b.d[5].p, offsets + ch.r0, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, c->copy_stream))) return hip_fail(e);
-        if ((e = hipEventRecord(b.ev_total, c->copy_stream))) return hip_fail(e);
+        if ((r = bank_scratch(c, b, kSlotBytes, b.n + 16))) return r;
+        if ((r = bank_scratch(c, b, kSlotOffsets, (size_t)(nrec + 1) * 8))) return r;
+        if ((r = bank_scratch(c, b, kSlotMinBytes, (size_t)nrec * m))) return r;
+        if ((r = bank_scratch(c, b, kSlotMinPos, (size_t)nrec * 8))) return r;
+        if ((r = bank_scratch(c, b, kSlotMinStrand, (size_t)nrec))) return r;
+        if ((r = bank_scratch(c, b, kSlotBest, 64))) return r;
+        HIPCHK(hipMemcpyAsync(b.at<uint8_t>(kSlotBytes), seq + offsets[b.r0], b.n, hipMemcpyHostToDevice, c->copy_stream));
+        HIPCHK(hipMemcpyAsync(b.at<uint64_t>(kSlotOffsets), offsets + b.r0, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, c->copy_stream));
+        HIPCHK(hipEventRecord(b.ev_ready, c->copy_stream));
         return NTK_OK;
     };
-    auto compute_and_download = [&](size_t ci) -> int {
-        const Chunk &ch = chunks[ci];
-        CompatBank &b = c->bank[ci % kBanks];
-        const uint64_t nrec = ch.r1 - ch.r0;
-        hipError_t e;
-        if ((e = hipStreamWaitEvent(c->stream, b.ev_total, 0))) return hip_fail(e);
-        if ((e = hipMemsetAsync(b.d[4].p, 0xFF, 8, c->stream))) return hip_fail(e);
+    auto compute_and_download = [&](CompatBank &b) -> int {
+        const uint64_t nrec = b.nrec;
+        const uint8_t *d_bytes = b.at<uint8_t>(kSlotBytes);
+        uint8_t *d_min = b.at<uint8_t>(kSlotMinBytes), *d_strand = b.at<uint8_t>(kSlotMinStrand);
+        uint64_t *d_pos = b.at<uint64_t>(kSlotMinPos);
+        HIPCHK(hipStreamWaitEvent(c->stream, b.ev_ready, 0));
+        HIPCHK(hipMemsetAsync(b.at<uint64_t>(kSlotBest), 0xFF, 8, c->stream));
         const uint64_t blocks = (nrec + 3) / 4;
         hipLaunchKernelGGL(minimizer_batch_kernel, dim3((unsigned)(blocks < (uint64_t)c->n_cu * 16 ? blocks : (uint64_t)c->n_cu * 16)), dim3(256), 0, c->stream,
-                           (const uint8_t *)b.d[0].p, (const uint64_t *)b.d[5].p, nrec, m, kLongRecord, comp, (uint8_t *)b.d[2].p, (uint64_t *)b.d[3].p,
-                           (uint8_t *)b.d[1].p, (unsigned long long *)b.d[4].p);
-        for (uint64_t r = ch.r0; r < ch.r1; r++) {   // the rare long record: the one-block kernel of ntk_minimizer, on the uploaded bytes
+                           d_bytes, b.at<const uint64_t>(kSlotOffsets), nrec, m, kLongRecord, comp, d_min, d_pos, d_strand, b.at<unsigned long long>(kSlotBest));
+        for (uint64_t r = b.r0; r < b.r0 + nrec; r++) {   // the rare long record: the one-block kernel of ntk_minimizer, on the uploaded bytes
             const uint64_t n = offsets[r + 1] - offsets[r];
             if (n <= kLongRecord) continue;
-            const uint8_t *rec = (const uint8_t *)b.d[0].p + (offsets[r] - offsets[ch.r0]);
-            uint64_t *d_best = (uint64_t *)b.d[4].p + 1;
+            const uint8_t *rec = d_bytes + (offsets[r] - offsets[b.r0]);
+            uint64_t *d_best = b.at<uint64_t>(kSlotBest) + 1;
             hipLaunchKernelGGL(minimizer_bytes_kernel, dim3(1), dim3(1024), 0, c->stream, rec, n, m, comp, d_best);
-            hipLaunchKernelGGL(minimizer_emit_record_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, rec, n, m, comp, (const uint64_t *)d_best, r - ch.r0,
-                               (uint8_t *)b.d[2].p, (uint64_t *)b.d[3].p, (uint8_t *)b.d[1].p);
+            hipLaunchKernelGGL(minimizer_emit_record_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, rec, n, m, comp, (const uint64_t *)d_best, r - b.r0,
+                               d_min, d_pos, d_strand);
         }
-        if ((e = hipGetLastError())) return hip_fail(e);
-        if ((e = hipEventRecord(b.ev_scattered, c->stream))) return hip_fail(e);
-        if ((e = hipStreamWaitEvent(c->down_stream, b.ev_scattered, 0))) return hip_fail(e);
-        if ((e = hipMemcpyAsync(out + ch.r0 * m, b.d[2].p, (size_t)nrec * m, hipMemcpyDeviceToHost, c->down_stream))) return hip_fail(e);
-        if (pos_out && (e = hipMemcpyAsync(pos_out + ch.r0, b.d[3].p, (size_t)nrec * 8, hipMemcpyDeviceToHost, c->down_stream))) return hip_fail(e);
-        if (is_rc_out && (e = hipMemcpyAsync(is_rc_out + ch.r0, b.d[1].p, (size_t)nrec, hipMemcpyDeviceToHost, c->down_stream))) return hip_fail(e);
-        if ((e = hipEventRecord(b.ev_done, c->down_stream))) return hip_fail(e);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(b.ev_computed, c->stream));
+        HIPCHK(hipStreamWaitEvent(c->down_stream, b.ev_computed, 0));
+        HIPCHK(hipMemcpyAsync(out + b.r0 * m, d_min, (size_t)nrec * m, hipMemcpyDeviceToHost, c->down_stream));
+        if (pos_out) HIPCHK(hipMemcpyAsync(pos_out + b.r0, d_pos, (size_t)nrec * 8, hipMemcpyDeviceToHost, c->down_stream));
+        if (is_rc_out) HIPCHK(hipMemcpyAsync(is_rc_out + b.r0, d_strand, (size_t)nrec, hipMemcpyDeviceToHost, c->down_stream));
+        HIPCHK(hipEventRecord(b.ev_landed, c->down_stream));
         b.busy = true;
         return NTK_OK;
     };
-    if (!chunks.empty()) rc = upload(0);
-    for (size_t ci = 0; ci < chunks.size() && rc == NTK_OK; ci++) {
-        if (ci + 1 < chunks.size() && (rc = upload(ci + 1))) break;
-        rc = compute_and_download(ci);
-    }
-    const hipError_t e0 = hipStreamSynchronize(c->down_stream);
-    const hipError_t e1 = e0 != hipSuccess ? e0 : hipStreamSynchronize(c->stream), e2 = hipStreamSynchronize(c->copy_stream);
-    for (CompatBank &b : c->bank) b.busy = false;
-    bank_trim(c);
-    if (rc != NTK_OK) return rc;
-    if (e1 != hipSuccess || e2 != hipSuccess) { g_last_hip = (int)(e1 != hipSuccess ? e1 : e2); return NTK_ERR_HIP; }
-    return NTK_OK;
+    return run_banked(c, offsets, n_records, 0, true, upload, compute_and_download, [](CompatBank &) {});
 }
 }  // namespace
 
@@ -1774,9 +1750,9 @@ int ntk_minimizer(ntk_ctx *c, const uint8_t *seq, uint64_t n, uint32_t m, uint8_
     uint64_t *d_best = (uint64_t *)(d_out + ((m + 15) & ~15u));
     HIPCHK(hipMemcpyAsync(d_in, seq, n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(minimizer_bytes_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint8_t *)d_in, n, m,
-                       (const uint16_t *)(c->d_lut + 768), d_best);
+                       c->lut_complement(), d_best);
     hipLaunchKernelGGL(minimizer_emit_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)d_in, n, m,
-                       (const uint16_t *)(c->d_lut + 768), (const uint64_t *)d_best, d_out);
+                       c->lut_complement(), (const uint64_t *)d_best, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out, m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1897,7 +1873,7 @@ int ntk_reverse_complement_records_device(ntk_ctx *c, const uint8_t *d_in, uint8
     HIPCHK(hipSetDevice(c->device));
     const uint64_t total = n_records * stride;
     hipLaunchKernelGGL(revcomp_records_kernel, dim3(grid_for(total, 256)), dim3(256), 0, c->stream,
-                       d_in, d_out, n_records, record_len, stride, (const uint16_t *)(c->d_lut + 768));
+                       d_in, d_out, n_records, record_len, stride, c->lut_complement());
     HIPCHK(hipGetLastError());
     return NTK_OK;
 }

@@ -14,8 +14,10 @@ CP_BLOCK_POSITIONS = 16384            # kCpThreads * kCpWords * 16: one block of
 PL_TILE = 2048                        # kPlThreads * kPlPer: one tile of the planes kernels; the grid is n_cu * PL_BLOCKS_PER_CU blocks
 PL_BLOCKS_PER_CU = 8
 GRID_CAP_ITEMS = (1 << 20) * 256      # grid_for: at most 2^20 blocks of 256 threads; beyond that a thread takes a second item
-LONG_RECORD = 1 << 16                 # minimizer_batch_impl: longer records go to the one-block kernel
-DEFAULT_CHUNK_BYTES = 16 * MI         # ntk_ctx::compat_chunk
+LONG_RECORD = 1 << 16                 # kLongRecord (ntk_compat_plan.hpp): ntk_minimizer_batch hands longer records to the one-block kernel
+DEFAULT_CHUNK_BYTES = 16 * MI         # kCompatChunkBytes: ntk_ctx::compat_chunk by default
+MIN_CHUNK_BYTES = 64                  # kCompatChunkMin: the least NTK_OPT_COMPAT_CHUNK_BYTES is set to
+BANKS = 3                             # kCompatBanks: the chunks the batched calls keep in flight
 
 
 def first_difference(got, want):
@@ -203,3 +205,44 @@ def minimizer_batch_records():
     small = b"GATTACAGATTACA"
     return [small, _random_bases(rng, LONG_RECORD - 1), _random_bases(rng, LONG_RECORD), _random_bases(rng, LONG_RECORD + 1), b"AC" * 100_000,
             _random_bases(rng, 70_000), b"TTTTTTTTTTTTTTTTTTTTTTTTT"]
+
+
+# ---- the chunk pipeline of the batched calls (tests/test_gpu_parity.py; tests/test_compat_plan.py cuts the same lists on the CPU) --------
+def parity_item_records():
+    """The batch of test_batched_compat_face_matches_the_iterators_per_record: ragged, empty and all-N records, mixed case."""
+    rng = np.random.default_rng(21)
+    alphabet = np.frombuffer(b"ACGTACGTACGTacgtNn-", dtype=np.uint8)
+    records = [b"", b"A", b"N" * 40, b"ACGT" * 10, b"acgtACGTnACGTTGCA" * 3]
+    for _ in range(400):
+        records.append(bytes(alphabet[rng.integers(0, len(alphabet), int(rng.integers(0, 400)))]))
+    records += [b"", bytes(alphabet[rng.integers(0, 4, 3000)])]
+    return records
+
+
+def parity_bit_plane_records():
+    """The batch of test_bit_kmers_planes_face_matches_the_iterator_per_record: as above, with U (a break on the bit path) and palindromes."""
+    rng = np.random.default_rng(57)
+    alphabet = np.frombuffer(b"ACGTACGTACGTacgtNnU-", dtype=np.uint8)
+    records = [b"", b"A", b"N" * 40, b"ACGT" * 10, b"acgtACGTnACGTTGCA" * 3, b"AATT", b"GAATTC" * 6]
+    for _ in range(300):
+        records.append(bytes(alphabet[rng.integers(0, len(alphabet), int(rng.integers(0, 400)))]))
+    records.append(bytes(rng.choice(list(b"ACGT"), size=5000).astype(np.uint8)))
+    return records
+
+
+PIPELINE_CHUNK_OPTIONS = (64, 97)     # the NTK_OPT_COMPAT_CHUNK_BYTES values at which the two kinds of batch below are run
+PIPELINE_RECORD_LEN = 40              # 40 + 1 <= 64 < 2 * (40 + 1) and 40 <= 64 < 2 * 40: one record per chunk at 64, packed or not
+PIPELINE_BATCH_SIZES = (1, 2, 3, 4, 7)   # chunk counts below, at and above BANKS, and past two turns of the banks
+
+
+def empties_around_oversize():
+    """Chunks of nothing but empty records on both sides of a record larger than the chunk: {0}, {1}, {2, 3} where records are uploaded
+    as they lie; with a break byte per record at a chunk of 64, {0}, {1}, {2, 3} as well (1 <= 64 < 102; 2 <= 64)."""
+    return [b"", b"ACGT" * 25, b"", b""]
+
+
+def bank_count_batches():
+    """Batches of 1, 2, 3, 4 and 7 records of PIPELINE_RECORD_LEN bytes (mixed case, an N): chunk counts around the bank count."""
+    rng = np.random.default_rng(0xBA)
+    letters = np.frombuffer(b"ACGT" * 6 + b"acgtN", dtype=np.uint8)
+    return [[bytes(letters[rng.integers(0, len(letters), PIPELINE_RECORD_LEN)]) for _ in range(n)] for n in PIPELINE_BATCH_SIZES]

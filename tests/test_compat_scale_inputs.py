@@ -1,5 +1,5 @@
 """The inputs of tests/test_gpu_compat_scale.py are past the thresholds they aim at - proven without a GPU, from the input builders
-(tests/_compat_scale.py), the oracle and the constants in the source text.  A changed constant fails here rather than silently
+(tests/_compat_scale.py), the oracle, the constants in the source text and those csrc/ntk_compat_plan.hpp states when compiled.  A changed constant fails here rather than silently
 un-covering a branch of compact_scan_kernel, cp_scan_kernel, the planes kernels' tile loop, grid_for's cap or the long-record hand-over."""
 import os
 import re
@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import _compat_plan as P
 import _compat_scale as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,18 +25,18 @@ def _const(text, name):
 
 
 @pytest.fixture(scope="module")
-def consts(src):
+def consts(src, tmp_path_factory):
     k, api = src["ntk_kernels.hpp"], src["ntk_api.hip"]
-    chunk = re.search(r"uint64_t compat_chunk = \(uint64_t\)(\d+) << (\d+);", api)
-    long_rec = re.search(r"int minimizer_batch_impl\(.*?constexpr uint64_t kLongRecord = (\d+)ull << (\d+);", api, re.S)
+    plan = P.build(tmp_path_factory.mktemp("compat_plan"))   # the default chunk, the long-record threshold and the bank count: asked of the header
     grid = re.search(r"inline unsigned grid_for\(uint64_t items, unsigned block\) \{.*?b > \(1u << (\d+)\) \? \(1u << (\d+)\)", api)
     assert grid.group(1) == grid.group(2)
     return {
         "compact_block": _const(k, "kCompactThreads") * _const(k, "kCompactPerThread"),
         "cp_block": _const(k, "kCpThreads") * _const(k, "kCpWords") * 16,
         "pl_tile": _const(k, "kPlThreads") * _const(k, "kPlPer"),
-        "chunk": int(chunk.group(1)) << int(chunk.group(2)),
-        "long_record": int(long_rec.group(1)) << int(long_rec.group(2)),
+        "chunk": plan.plan_default_chunk(),
+        "long_record": plan.plan_long_record(),
+        "banks": plan.plan_banks(),
         "grid_cap_blocks": 1 << int(grid.group(1)),
     }
 
@@ -52,6 +53,11 @@ def test_kernel_constants_are_the_tests(src, consts):
     assert re.search(r"kPlTile = kPlThreads \* kPlPer;", k)
     assert consts["chunk"] == S.DEFAULT_CHUNK_BYTES
     assert consts["long_record"] == S.LONG_RECORD
+    assert consts["banks"] == S.BANKS
+    # ... and the library uses the header's numbers: the ctx's default and its option, the banks it keeps, the hand-over below
+    assert re.search(r"uint64_t compat_chunk = kCompatChunkBytes;", api)
+    assert re.search(r"c->compat_chunk = value == 0 \? kCompatChunkBytes : \(value < kCompatChunkMin \? kCompatChunkMin : value\);", api)
+    assert re.search(r"CompatBank bank\[kCompatBanks\];", api) and not re.search(r"\bkLongRecord = ", api)
     assert consts["grid_cap_blocks"] * 256 == S.GRID_CAP_ITEMS
     # both scans are launched as ONE block of 1024 threads and split their work on that number
     assert re.search(r"hipLaunchKernelGGL\(compact_scan_kernel, dim3\(1\), dim3\(1024\)", api)

@@ -11,6 +11,7 @@ torch = pytest.importorskip("torch")
 
 import needletail_amd as nt  # noqa: E402
 import oracle as O  # noqa: E402  (the checker)
+import _compat_scale as CS  # noqa: E402
 from _fastx import bgzf_compress, fasta_raw_seqs, fastq_raw_seqs  # noqa: E402
 
 
@@ -1635,7 +1636,7 @@ def test_bench_plain_run_is_lean(tmp_path):
     assert np.array_equal(np.load(tmp_path / "out" / "hist.npy").astype(np.uint64), np.asarray(want["hist"], dtype=np.uint64))
 
 
-@pytest.mark.parametrize("chunk_bytes", [None, 97, 4096])
+@pytest.mark.parametrize("chunk_bytes", [None, 64, 97, 4096])
 def test_batched_compat_face_matches_the_iterators_per_record(ctx, chunk_bytes, restore_options):
     """ntk_bit_kmers_batch / ntk_canonical_kmers_batch: one call for a whole batch of records, element-wise against the
     oracle's literal iterators (reference src/sequence.rs:237-252) record by record; ragged, empty and all-N records,
@@ -1643,12 +1644,27 @@ def test_batched_compat_face_matches_the_iterators_per_record(ctx, chunk_bytes, 
     flight, 16 MiB of packed bytes each); NTK_OPT_COMPAT_CHUNK_BYTES = 97 / 4096 forces hundreds of chunks out of this small batch:
     chunks of one record, records larger than a chunk, the capacity running out in the middle of a chunk."""
     ctx.set_option(NL.OPT_COMPAT_CHUNK_BYTES, chunk_bytes or 0)   # (restored at the end of the test)
-    rng = np.random.default_rng(21)
-    alphabet = np.frombuffer(b"ACGTACGTACGTacgtNn-", dtype=np.uint8)
-    records = [b"", b"A", b"N" * 40, b"ACGT" * 10, b"acgtACGTnACGTTGCA" * 3]
-    for _ in range(400):
-        records.append(bytes(alphabet[rng.integers(0, len(alphabet), int(rng.integers(0, 400)))]))
-    records += [b"", bytes(alphabet[rng.integers(0, 4, 3000)])]
+    records = CS.parity_item_records()
+    # the pipeline at its edges: chunks of nothing but empty records around a record larger than the chunk, and as many chunks as there
+    # are banks, fewer and more; the faces run back to back on the one ctx, so the banks change role from call to call
+    if chunk_bytes in CS.PIPELINE_CHUNK_OPTIONS:
+        for recs in [CS.empties_around_oversize()] + CS.bank_count_batches():
+            for k in (4, 21):
+                counts, pos, val, flg = nt.bit_kmers_batch(recs, k, True, ctx)
+                want = [O.bit_kmers_arrays(r, k, True) for r in recs]
+                assert counts.tolist() == [len(w[0]) for w in want], (k, len(recs))
+                for j, got in enumerate((pos, val, flg)):
+                    assert np.array_equal(got, np.concatenate([w[j] for w in want])), (k, len(recs), j)
+                counts, pos, flg = nt.canonical_kmers_batch(recs, k, ctx)
+                want = [O.canonical_kmers_arrays(r, O.reverse_complement(r), k) for r in recs]
+                assert counts.tolist() == [len(w[0]) for w in want], (k, len(recs))
+                for j, got in enumerate((pos, flg)):
+                    assert np.array_equal(got, np.concatenate([w[j] for w in want])), (k, len(recs), j)
+                pl = nt.canonical_kmers_planes(recs, k, ctx)
+                for i, w in enumerate(want):
+                    gp, gf = pl.arrays(i)
+                    assert np.array_equal(gp, w[0]) and np.array_equal(gf, w[1]), (k, len(recs), i)
+                assert pl.total == sum(len(w[0]) for w in want) and int(pl.rec_bit[-1]) == 16 * len(pl.valid16)
     for k, canonical in ((1, True), (4, False), (21, True), (31, True), (32, False)):
         counts, pos, val, flg = nt.bit_kmers_batch(records, k, canonical, ctx)
         assert len(counts) == len(records)
@@ -1906,7 +1922,7 @@ def test_reset_flag_starts_a_new_result(ctx, monkeypatch):
 from _refs import minimizer_with_position as _ref_minimizer_with_position  # noqa: E402
 
 
-@pytest.mark.parametrize("chunk_bytes", [None, 97, 4096])
+@pytest.mark.parametrize("chunk_bytes", [None, 64, 97, 4096])
 def test_minimizer_batch_matches_the_reference_function_per_record(ctx, restore_options, chunk_bytes):
     """ntk_minimizer_batch = sequence::minimizer (reference src/sequence.rs:139-152) applied to every record of a reader batch in one call:
     raw-byte comparison (mixed case, N, IUPAC, U - complement() maps what it maps), homopolymers and repeats (ties: the reference's loop order
@@ -1920,6 +1936,10 @@ def test_minimizer_batch_matches_the_reference_function_per_record(ctx, restore_
     alphabet = np.frombuffer(b"ACGTACGTACGTACGTacgtNnURYKMSWBDHV", dtype=np.uint8)
     assert nt.minimizer_batch([b"ATTTCG"], 3, ctx) == [b"AAA"]                      # reference src/sequence.rs:363-367
     assert nt.minimizer_batch([], 5, ctx) == []
+    if chunk_bytes in CS.PIPELINE_CHUNK_OPTIONS:   # as many chunks as there are banks, fewer and more
+        for recs in CS.bank_count_batches():
+            mins, pos, flg = nt.minimizer_batch(recs, 8, ctx, with_positions=True)
+            assert [(mins[r], int(pos[r]), int(flg[r])) for r in range(len(recs))] == [_ref_minimizer_with_position(rec, 8) for rec in recs], len(recs)
     for m in (1, 2, 3, 8, 15, 21, 31, 40):
         recs = [bytes(alphabet[rng.integers(0, len(alphabet), int(n))]) for n in rng.integers(m, 300, 120)]
         recs += [b"A" * m, b"T" * (m + 5), b"AC" * (m + 3), bytes(rng.choice(list(b"ACGT"), size=m).astype(np.uint8))]
@@ -1952,7 +1972,7 @@ def test_minimizer_batch_matches_the_reference_function_per_record(ctx, restore_
         nt.minimizer_batch([b"ACGTACGT", b"ACG", b"ACGTACGT"], 5, ctx)
 
 
-@pytest.mark.parametrize("chunk_bytes", [None, 97, 4096])
+@pytest.mark.parametrize("chunk_bytes", [None, 64, 97, 4096])
 def test_bit_kmers_planes_face_matches_the_iterator_per_record(ctx, chunk_bytes, restore_options):
     """ntk_bit_kmers_batch_planes = Sequence::bit_kmers(k, canonical) (reference src/sequence.rs:250-252, src/bitkmer.rs:39-143) for every record
     of a batch as "emitted" / "was_rc" planes per window start + dense packed values: element-wise against the oracle's literal iterator,
@@ -1960,12 +1980,15 @@ def test_bit_kmers_planes_face_matches_the_iterator_per_record(ctx, chunk_bytes,
     (ties keep the forward k-mer), records touching chunk boundaries (the three-bank pipeline over hundreds of chunks) - with the values
     downloaded and with the values packed on the host from the planes."""
     ctx.set_option(NL.OPT_COMPAT_CHUNK_BYTES, chunk_bytes or 0)
-    rng = np.random.default_rng(57)
-    alphabet = np.frombuffer(b"ACGTACGTACGTacgtNnU-", dtype=np.uint8)
-    records = [b"", b"A", b"N" * 40, b"ACGT" * 10, b"acgtACGTnACGTTGCA" * 3, b"AATT", b"GAATTC" * 6]
-    for _ in range(300):
-        records.append(bytes(alphabet[rng.integers(0, len(alphabet), int(rng.integers(0, 400)))]))
-    records.append(bytes(rng.choice(list(b"ACGT"), size=5000).astype(np.uint8)))
+    records = CS.parity_bit_plane_records()
+    # the pipeline at its edges (see test_batched_compat_face_matches_the_iterators_per_record)
+    if chunk_bytes in CS.PIPELINE_CHUNK_OPTIONS:
+        for recs in [CS.empties_around_oversize()] + CS.bank_count_batches():
+            for canonical in (True, False):
+                pl = nt.bit_kmers_planes(recs, 4, canonical, ctx)
+                want = [O.bit_kmers(r, 4, canonical) for r in recs]
+                assert [list(pl.iter(i)) for i in range(len(recs))] == want, (canonical, len(recs))
+                assert pl.total == sum(len(w) for w in want)
     for k in (1, 2, 4, 11, 16, 17, 21, 31, 32):
         for canonical in (True, False):
             pl = nt.bit_kmers_planes(records, k, canonical, ctx)

@@ -15,15 +15,6 @@
 
 #include "ntk_tile.hpp"
 
-// Ablation switches (NTK_ABL_*: loads only, floor kernel, no LDS atomics, no digests, no exec writes, no SDWA compares, no mask algebra) and
-// the per-wave clock census (NTK_V_CLOCKS) exist for tools/kbench.hip alone, which is built with -DNTK_KBENCH: they produce WRONG results
-// by design and measure what a class of the tile loop costs (profiles/r03c/ablation.txt, r04i/ablation.txt).  No product object may see one.
-#if !defined(NTK_KBENCH) && (defined(NTK_ABL_LOADSONLY) || defined(NTK_ABL_FLOOR) || defined(NTK_ABL_NOLDS) || defined(NTK_ABL_NODIGEST) || \
-                             defined(NTK_ABL_NOEXEC) || defined(NTK_ABL_NOSDWA) || defined(NTK_ABL_NOMASKALG) || defined(NTK_V_CLOCKS) || \
-                             defined(NTK_X_CMPFIRST) || defined(NTK_X_TWOPHASE) || defined(NTK_X_MFMASUM) || defined(NTK_X_SELOUT) || defined(NTK_X_PREFETCH2) || defined(NTK_ABL_HALFIMPORTS))
-#error "NTK_ABL_* / NTK_X_* / NTK_V_CLOCKS are kernel-bench switches: build with -DNTK_KBENCH (tools/build_kbench.sh), never into the library"
-#endif
-
 namespace ntk {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -278,20 +269,11 @@ struct DevMasks2 {
     uint32_t one = 1;
     uint32_t nf_s = 0;            // forward-strand count of the WAVE (scalar: s_bcnt1 of the compare mask, no LDS op, no VALU op)
     uint32_t nf_bits = 0;         // fused minimizers: per-lane sum of the chosen keys' strand bits
-#ifdef NTK_X_MFMASUM
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    i32x4 macc = {0, 0, 0, 0}, msel = {0, 0, 0, 0};   // kbench experiment: byte sums on the matrix pipe (see emit_canon)
-#endif
 
     template <int KM, bool EXACT, class Enc>   // KM: good bases a window needs (K: EXACT, the tile geometry of the k-mer builds - or K + W - 1 for windowed minimizers)
     __device__ __forceinline__ void compute(const Enc &en, bool tail_tile, int64_t lane_base, uint64_t n_bytes)
     {
         uint64_t B[16];
-#ifdef NTK_ABL_NOSDWA
-#pragma unroll
-        for (int i = 0; i < 16; i++) B[i] = __builtin_amdgcn_ballot_w64(en.ex[i & 3] != (uint32_t)i);
-        if (false) {
-#endif
         NTK_SDWA_EQ(B[0], en.ex[0], en.uu[0], BYTE_0);  NTK_SDWA_EQ(B[1], en.ex[0], en.uu[0], BYTE_1);
         NTK_SDWA_EQ(B[2], en.ex[0], en.uu[0], BYTE_2);  NTK_SDWA_EQ(B[3], en.ex[0], en.uu[0], BYTE_3);
         NTK_SDWA_EQ(B[4], en.ex[1], en.uu[1], BYTE_0);  NTK_SDWA_EQ(B[5], en.ex[1], en.uu[1], BYTE_1);
@@ -300,19 +282,11 @@ struct DevMasks2 {
         NTK_SDWA_EQ(B[10], en.ex[2], en.uu[2], BYTE_2); NTK_SDWA_EQ(B[11], en.ex[2], en.uu[2], BYTE_3);
         NTK_SDWA_EQ(B[12], en.ex[3], en.uu[3], BYTE_0); NTK_SDWA_EQ(B[13], en.ex[3], en.uu[3], BYTE_1);
         NTK_SDWA_EQ(B[14], en.ex[3], en.uu[3], BYTE_2); NTK_SDWA_EQ(B[15], en.ex[3], en.uu[3], BYTE_3);
-#ifdef NTK_ABL_NOSDWA
-        }
-#endif
         if (tail_tile) {  // wave-uniform: bytes at or beyond n_bytes are breaks (the last 16-B line may carry padding)
 #pragma unroll
             for (int i = 0; i < 16; i++) B[i] &= __builtin_amdgcn_ballot_w64(lane_base + i < (int64_t)n_bytes);
         }
-#ifdef NTK_ABL_NOMASKALG
-#pragma unroll
-        for (int i = 0; i < 16; i++) { VA[i] = B[i]; VB[i] = ~0ull; }
-#else
         window_masks_ab_any<KM, EXACT>(B, VA, VB);
-#endif
     }
 
     // unsigned minimum of two keys that are positive doubles (bit 63 clear; not NaN / infinity: the exponent field is never all ones): one v_min_f64
@@ -356,28 +330,14 @@ struct DevMasks2 {
     // complement value, fl / rl = their lo words, o = histogram cell offset, t = the chosen lo word.
     // Measured against the round-2 region (exec move; atomic; mad; xor; exec AND; own-cell atomic): -6.5 % kernel time at k = 21
     // (profiles/r03a): every exec write stalls the VALU for ~3 cycles and LDS ops are the most expensive instructions of the loop.
-#ifdef NTK_ABL_NOEXEC    // ablation: exec is never narrowed (what a tile without breaks could run, were it not for the halo lanes)
-#define NTK_R_EXEC(i) ""
-#else
 #define NTK_R_EXEC(i) "s_and_b64 exec, %[A" #i "], %[B" #i "]\n"
-#endif
 #define NTK_R_MASKS(i) [A##i] "s"(VA[pos[i]]), [B##i] "s"(VB[pos[i]])
-#ifdef NTK_ABL_NOLDS      // ablations of tools/kbench.hip (wrong results, same instruction stream otherwise)
-#define NTK_R_HIST(i) ""
-#else
 #define NTK_R_HIST(i) "ds_add_u32 %[o" #i "], %[one]\n"
-#endif
 #define NTK_R_CNT_FIRST "s_bcnt1_i32_b64 %[nf], vcc\n"                                   /* the block's first position starts its count */
 #define NTK_R_CNT "s_bcnt1_i32_b64 %[cn], vcc\n s_add_u32 %[nf], %[nf], %[cn]\n"
-#ifdef NTK_ABL_NODIGEST
-#define NTK_R_SUM_0(x) ""
-#define NTK_R_SUM_1(x) ""
-#define NTK_R_XOR(x) ""
-#else
 #define NTK_R_SUM_0(x) "v_mad_u64_u32 %[sumA], %[sd], " x ", 1, %[sumA]\n"
 #define NTK_R_SUM_1(x) "v_mad_u64_u32 %[sumB], %[sd], " x ", 1, %[sumB]\n"
 #define NTK_R_XOR(x) "v_xor_b32 %[xlo], %[xlo], " x "\n"
-#endif
 #define NTK_R_SUM_2(x) NTK_R_SUM_0(x)
 #define NTK_R_SUM_3(x) NTK_R_SUM_1(x)
 
@@ -405,94 +365,8 @@ struct DevMasks2 {
           [sd] "=&s"(sd), [nf] "=&s"(nf_grp), [cn] "=&s"(cn)                                                                             \
         : NTK_R_IN(0), NTK_R_IN(1), NTK_R_IN(2), NTK_R_IN(3), [one] "v"(one)                                                            \
         : "memory", "vcc", "scc"
-#if defined(NTK_X_CMPFIRST)
-        // round-6 experiment (a), profiles/r06a: the four strand compares leave the region - under the full exec mask, each into its own
-        // SGPR pair, scheduled by the compiler among the window words - and the region keeps exec, select, digests, atomic, count
-        uint64_t F[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) F[i] = __builtin_amdgcn_ballot_w64(TIE_RC_ ? ft[i] < rt[i] : ft[i] <= rt[i]);
-#define NTK_X_POS(i, CNT)                                                   \
-        NTK_R_EXEC(i)                                                       \
-        "s_and_b64 vcc, exec, %[F" #i "]\n"                                 \
-        "v_cndmask_b32 %[t" #i "], %[rl" #i "], %[fl" #i "], vcc\n"          \
-        NTK_R_SUM_##i("%[t" #i "]")                                         \
-        NTK_R_XOR("%[t" #i "]")                                             \
-        NTK_R_HIST(i)                                                       \
-        CNT
-#define NTK_X_IN(i) [o##i] "v"(off[i]), [fl##i] "v"(fl[i]), [rl##i] "v"(rl[i]), [F##i] "s"(F[i]), NTK_R_MASKS(i)
-        asm volatile(NTK_X_POS(0, NTK_R_CNT_FIRST) NTK_X_POS(1, NTK_R_CNT) NTK_X_POS(2, NTK_R_CNT) NTK_X_POS(3, NTK_R_CNT) "s_mov_b64 exec, -1\n"
-                     : [sumA] "+v"(sum), [sumB] "+v"(sum2), [xlo] "+v"(xlo), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3),
-                       [sd] "=&s"(sd), [nf] "=&s"(nf_grp), [cn] "=&s"(cn)
-                     : NTK_X_IN(0), NTK_X_IN(1), NTK_X_IN(2), NTK_X_IN(3), [one] "v"(one)
-                     : "memory", "vcc", "scc");
-#undef NTK_X_IN
-#undef NTK_X_POS
-#elif defined(NTK_X_SELOUT)
-        // round-6 experiment (a''), profiles/r06j: compare AND select leave the region, as in the K >= 24 builds (emit_canon_wide) - under the
-        // full exec mask, scheduled by the compiler among the window words; the region keeps exec, the two digests, the atomic and the count
-        // (s_and of the compare's mask with exec + s_bcnt1 + s_add).  The k = 31 build, which has this shape, idles 41 cycles per tile where
-        // the k = 21 build idles 101.
-        uint64_t F[4], fm;
-        uint32_t ts[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const bool fwd = TIE_RC_ ? ft[i] < rt[i] : ft[i] <= rt[i];
-            F[i] = __builtin_amdgcn_ballot_w64(fwd);
-            ts[i] = fwd ? fl[i] : rl[i];
-        }
-#define NTK_X_POS(i, CNT)                                                   \
-        NTK_R_EXEC(i)                                                       \
-        NTK_R_SUM_##i("%[t" #i "]")                                         \
-        NTK_R_XOR("%[t" #i "]")                                             \
-        NTK_R_HIST(i)                                                       \
-        "s_and_b64 %[fm], exec, %[F" #i "]\n"                               \
-        CNT
-#define NTK_X_CNT_FIRST "s_bcnt1_i32_b64 %[nf], %[fm]\n"
-#define NTK_X_CNT "s_bcnt1_i32_b64 %[cn], %[fm]\n s_add_u32 %[nf], %[nf], %[cn]\n"
-#define NTK_X_IN(i) [o##i] "v"(off[i]), [t##i] "v"(ts[i]), [F##i] "s"(F[i]), NTK_R_MASKS(i)
-        asm volatile(NTK_X_POS(0, NTK_X_CNT_FIRST) NTK_X_POS(1, NTK_X_CNT) NTK_X_POS(2, NTK_X_CNT) NTK_X_POS(3, NTK_X_CNT) "s_mov_b64 exec, -1\n"
-                     : [sumA] "+v"(sum), [sumB] "+v"(sum2), [xlo] "+v"(xlo), [sd] "=&s"(sd), [nf] "=&s"(nf_grp), [cn] "=&s"(cn), [fm] "=&s"(fm)
-                     : NTK_X_IN(0), NTK_X_IN(1), NTK_X_IN(2), NTK_X_IN(3), [one] "v"(one)
-                     : "memory", "scc");
-        (void)t0; (void)t1; (void)t2; (void)t3;
-#undef NTK_X_IN
-#undef NTK_X_CNT
-#undef NTK_X_CNT_FIRST
-#undef NTK_X_POS
-#elif defined(NTK_X_TWOPHASE)
-        // round-6 experiment (a'), profiles/r06a: the chain cut in two - first exec / compare / select / count of all four positions, then
-        // exec / digests / atomic of all four: the select's result is not needed for ~10 instructions, at the price of four more exec writes
-#define NTK_X_P1(i, CMP, CNT) NTK_R_EXEC(i) CMP " vcc, %[ft" #i "], %[rt" #i "]\n" "v_cndmask_b32 %[t" #i "], %[rl" #i "], %[fl" #i "], vcc\n" CNT
-#define NTK_X_P2(i) NTK_R_EXEC(i) NTK_R_SUM_##i("%[t" #i "]") NTK_R_XOR("%[t" #i "]") NTK_R_HIST(i)
-#define NTK_X_BODY(CMP) NTK_X_P1(0, CMP, NTK_R_CNT_FIRST) NTK_X_P1(1, CMP, NTK_R_CNT) NTK_X_P1(2, CMP, NTK_R_CNT) NTK_X_P1(3, CMP, NTK_R_CNT) \
-                        NTK_X_P2(0) NTK_X_P2(1) NTK_X_P2(2) NTK_X_P2(3) "s_mov_b64 exec, -1\n"
-        if constexpr (TIE_RC_) asm volatile(NTK_X_BODY("v_cmp_lt_u32") NTK_R_OPS);
-        else asm volatile(NTK_X_BODY("v_cmp_le_u32") NTK_R_OPS);
-#undef NTK_X_BODY
-#undef NTK_X_P2
-#undef NTK_X_P1
-#elif defined(NTK_X_MFMASUM)
-        // round-6 experiment (b), profiles/r06a: the sum of the lo words leaves the VALU - the chosen words are zero outside the window's
-        // lanes (four full-rate moves before the region) and ONE v_mfma_i32_16x16x64_i8 adds the sixteen bytes a lane holds, by significance,
-        // against a 0/1 selector.  TIMING PROXY: i8 is signed, so the byte sums are off by 256 x (bytes with the top bit set), which an exact
-        // version would have to count with more VALU work (tools/gen_ubench14.py prices that); n_total / n_fwd / xor / histogram stay exact.
-        t0 = t1 = t2 = t3 = 0;
-        asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
-#define NTK_X_POS(i, CMP, CNT) NTK_R_EXEC(i) CMP " vcc, %[ft" #i "], %[rt" #i "]\n" "v_cndmask_b32 %[t" #i "], %[rl" #i "], %[fl" #i "], vcc\n" NTK_R_XOR("%[t" #i "]") NTK_R_HIST(i) CNT
-#define NTK_X_BODY(CMP) NTK_X_POS(0, CMP, NTK_R_CNT_FIRST) NTK_X_POS(1, CMP, NTK_R_CNT) NTK_X_POS(2, CMP, NTK_R_CNT) NTK_X_POS(3, CMP, NTK_R_CNT) "s_mov_b64 exec, -1\n"
-#define NTK_X_OPS : [xlo] "+v"(xlo), [t0] "+v"(t0), [t1] "+v"(t1), [t2] "+v"(t2), [t3] "+v"(t3), [nf] "=&s"(nf_grp), [cn] "=&s"(cn) \
-                  : NTK_R_IN(0), NTK_R_IN(1), NTK_R_IN(2), NTK_R_IN(3), [one] "v"(one) : "memory", "vcc", "scc"
-        if constexpr (TIE_RC_) asm volatile(NTK_X_BODY("v_cmp_lt_u32") NTK_X_OPS);
-        else asm volatile(NTK_X_BODY("v_cmp_le_u32") NTK_X_OPS);
-        (void)sd;
-        macc = __builtin_amdgcn_mfma_i32_16x16x64_i8(i32x4{(int)t0, (int)t1, (int)t2, (int)t3}, msel, macc, 0, 0, 0);
-#undef NTK_X_OPS
-#undef NTK_X_BODY
-#undef NTK_X_POS
-#else
         if constexpr (TIE_RC_) asm volatile(NTK_R_BODY("v_cmp_lt_u32") NTK_R_OPS);   // byte path: ties report the reverse complement (src/kmer.rs:124-128)
         else asm volatile(NTK_R_BODY("v_cmp_le_u32") NTK_R_OPS);                     // bit path: ties stay forward (src/bitkmer.rs:136-143)
-#endif
         nf_s += nf_grp;
 #undef NTK_R_OPS
 #undef NTK_R_BODY
@@ -705,10 +579,6 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
     uint64_t *const s_red = L.red;
     if ((uint32_t)(uintptr_t)&L.hist[0] != 0u) __builtin_trap();
 
-#ifdef NTK_V_CLOCKS
-    const uint64_t dbg_c0 = clock64(), dbg_w0 = wall_clock64();
-    uint32_t dbg_tiles = 0;
-#endif
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t shard = blockIdx.x % a.n_shards;
@@ -738,32 +608,13 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
     DevMasks2<K, HB> mp;
     NoSink sink;
     mp.rep = lane & (uint32_t)(DevMasks2<K, HB>::kWordCopies - 1);
-#ifdef NTK_X_MFMASUM
-    { const int sel = 1 << (8 * (lane & 3)); mp.msel = {sel, sel, sel, sel}; }   // B[k][j] = [k % 4 == j % 4]: column j sums the bytes of significance j % 4
-#endif
 
     next = __builtin_amdgcn_readfirstlane(next);
-#ifdef NTK_X_GUIDED   // kbench experiment (profiles/r06q): the pulls shrink over a shard's last stretch (remaining / (2 x the shard's waves), at least 2 tiles)
-    uint32_t c_cur = a.chunk_tiles;
-    const uint32_t shard_waves2 = 2u * ((gridDim.x + a.n_shards - 1) / a.n_shards) * (blockDim.x >> 6);
-#endif
     while (next < shard_tiles) {
         const uint32_t r0 = shard_begin + next;
-#ifdef NTK_X_GUIDED
-        uint32_t r1 = r0 + c_cur;
-        if (r1 > shard_end) r1 = shard_end;
-        {
-            const uint32_t done = next + c_cur < shard_tiles ? next + c_cur : shard_tiles;
-            uint32_t c = (shard_tiles - done) / shard_waves2;
-            c = c < 2u ? 2u : (c > a.chunk_tiles ? a.chunk_tiles : c);
-            c_cur = c;
-            if (lane == 0) next = atomicAdd(ctr, c);
-        }
-#else
         uint32_t r1 = r0 + a.chunk_tiles;
         if (r1 > shard_end) r1 = shard_end;
         if (lane == 0) next = atomicAdd(ctr, a.chunk_tiles);
-#endif
         const uint64_t t0 = a.tile_begin + r0;
         const uint64_t run_byte = t0 * kStride;
         const uint32_t halo = t0 ? kHaloB : 0u;
@@ -783,18 +634,8 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
         }
         uint32_t voff = lane * 16u - (kHaloB - halo);
         uint64_t tile_byte = run_byte;
-#ifdef NTK_ABL_FLOOR
-        auto load_tile = [&](uint32_t off) { (void)rs; return u32x4{off, off, off, off}; };
-#else
         auto load_tile = [&](uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0); };
-#endif
         auto load_qual = [&](uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b128(rq, off, 0, 0); };
-#ifdef NTK_ABL_FLOOR
-        uint32_t fl_code = lane * 0x9E3779B9u + r0, fl_rcode = ~fl_code, fl_step = 0x85EBCA6Bu + lane;
-        asm volatile("" : "+v"(fl_step));
-#pragma unroll
-        for (int i = 0; i < 16; i++) { mp.VA[i] = ~3ull; mp.VB[i] = ~0ull; }
-#endif
         auto process = [&](const u32x4 &t, const u32x4 &q, uint32_t r, auto &&after_encode) {
             const bool tail = r >= a.tail_tile_rel;
             Raw16 raw{t.x, t.y, t.z, t.w};
@@ -807,17 +648,6 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
                 if (tail) lc |= or_of_input_bytes(lower_watch16(raw), (int64_t)a.n_bytes - ((int64_t)tile_byte - (int64_t)kHaloB + lane * 16));
                 else lc = lower_watch_or(lower_watch_or(lower_watch_or(lower_watch_or(lc, raw.x), raw.y), raw.z), raw.w);
             }
-#ifdef NTK_ABL_LOADSONLY
-            mp.xlo ^= raw.x ^ raw.y ^ raw.z ^ raw.w; (void)tail;
-            after_encode();
-#elif defined(NTK_ABL_FLOOR)
-            // floor kernel (tools/kbench.hip, profiles/r03*/floor.txt): no load, no encode, no validity - only the window words and
-            // the per-position work, on synthetic register-resident stream words (two adds keep them changing from tile to tile)
-            (void)tail; (void)raw;
-            after_encode();
-            fl_code += fl_step; fl_rcode += fl_code;
-            lane_tile_sv2<TIE_RC, K>(sink, xl, mp, fl_code, fl_rcode);
-#else
             const EncSV2 en = encode16_sv2<ACCEPT_U>(raw);
             mp.template compute<(W ? K + W - 1 : K), (W == 0)>(en, tail, (int64_t)tile_byte - (int64_t)kHaloB + lane * 16, a.n_bytes);
             after_encode();
@@ -825,11 +655,7 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
             else if constexpr (WORD) lane_tile_sv2w<TIE_RC, K, FWD>(sink, xl, mp, en.code, en.rcode);
             else if constexpr (FWD) lane_tile_sv2_fwd<K>(sink, xl, mp, en.code);
             else lane_tile_sv2<TIE_RC, K>(sink, xl, mp, en.code, en.rcode);
-#endif
             voff += kStride; tile_byte += kStride;
-#ifdef NTK_V_CLOCKS
-            dbg_tiles++;
-#endif
         };
         // The input's tile 0 starts kHaloB bytes before the buffer: a lane that lies wholly before it has a wrapped offset beyond num_records
         // and reads as 0.  Where kHaloB is no multiple of 16 one lane straddles byte 0, and how the hardware checks such an access (the offset
@@ -856,43 +682,19 @@ __global__ __launch_bounds__(1024, NTK_SV2_MINWAVES) void scan2_kernel(ScanArgs 
         // and 31, profiles/r03d/lateload_ab2.txt; two tiles per trip: 5 - 25 % slower, profiles/r02b, with the tile offset in the scalar
         // operand no gain, profiles/r03a/pp2_ab.txt; the first tile of the next chunk loaded during the last tile of this one: no gain,
         // profiles/r04b).
-#ifdef NTK_X_PREFETCH2
-        // round-6 experiment (profiles/r06k): TWO tiles in flight per wave (two register sets, the loop unrolled by two) - for the builds that
-        // are not held by VALU issue (forward-only: 110 VALU per tile, 27 % of the tile's cycles idle)
-        u32x4 tb = ta;
-        if (r0 + 1 < r1) tb = load_tile(voff + kStride);
-        for (uint32_t r = r0; r < r1; r += 2) {
-            process(ta, qa, r, [&] { if (r + 2 < r1) ta = load_tile(voff + 2 * kStride); });
-            if (r + 1 < r1) process(tb, qa, r + 1, [&] { if (r + 3 < r1) tb = load_tile(voff + 2 * kStride); });
-        }
-#else
         for (uint32_t r = r0; r < r1; r++)
             process(ta, qa, r, [&] {
                 if (r + 1 < r1) { ta = load_tile(voff + kStride); if constexpr (QM) qa = load_qual(voff + kStride); }
             });
-#endif
         next = __builtin_amdgcn_readfirstlane(next);
     }
 
-#ifdef NTK_V_CLOCKS
-    if ((threadIdx.x & 63) == 0 && a.values) {  // per-wave census (tools/kbench.hip): start, end of the tile loop, shader cycles | tiles << 40, placement
-        uint32_t hwid, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        const size_t w = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        a.values[w * 4 + 0] = dbg_w0; a.values[w * 4 + 1] = wall_clock64();
-        a.values[w * 4 + 2] = ((clock64() - dbg_c0) & 0xFFFFFFFFFFull) | ((uint64_t)dbg_tiles << 40); a.values[w * 4 + 3] = ((uint64_t)xcc << 32) | hwid;
-    }
-#endif
     if constexpr (SPEC)
         if (a.lower_flag && __builtin_amdgcn_ballot_w64((lc & 0x20202020u) != 0u) != 0ull && lane == 0) atomicOr(a.lower_flag, 1u);
     // wave -> block -> per-block partials (plain stores; the fold kernel sums them)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the asm blocks' LDS atomics are not tracked by the compiler
     // sum: the two alternating accumulators of the lo words, plus (K >= 24) the hi words' sum; xor: lo words, and (K >= 24) T words
     uint64_t sum = mp.sum + mp.sum2 + ((uint64_t)mp.sumh << 32);
-#ifdef NTK_X_MFMASUM
-    if ((lane & 15) < 4) sum += (uint64_t)(int64_t)(mp.macc.x + mp.macc.y + mp.macc.z + mp.macc.w) << (8 * (lane & 3));   // columns 0..3, all row groups
-#endif
     uint64_t xr = (WORD || LIGHT) ? (uint64_t)mp.xlo : ((uint64_t)mp.xh << 32) | mp.xlo, nf, nv = 0;
     uint64_t shi = 0, xf = 0;   // LIGHT: high parts of the digests, from the histogram
     uint32_t *ph = a.part_hist + (size_t)blockIdx.x * kHistBins;

@@ -1021,9 +1021,6 @@ NTK_HD void lane_tile_sv2(Sink &sink, XL &xl, MP &mp, uint32_t code, uint32_t rc
     // position and are fetched where that position is handled.
 #pragma unroll
     for (int g = 2; g <= D; g++) {
-#ifdef NTK_ABL_HALFIMPORTS   // kbench what-if (WRONG results): every other cross-lane word taken from the lane's own register - the most a longer lane pitch could save
-        if (g & 1) { fw[D - g] = fw[D + 16 - g]; continue; }
-#endif
         fw[D - g] = xl.prev(kSlotFw + 16 - g, fw[D + 16 - g]);
     }
     // Positions are taken in groups {jp, jp+1, jp+8, jp+9}: the T words of positions j and j+8 sit in ONE register on
@@ -1040,9 +1037,6 @@ NTK_HD void lane_tile_sv2(Sink &sink, XL &xl, MP &mp, uint32_t code, uint32_t rc
             const int j = pos[i];
             ft[i] = fw[j]; rt[i] = rw[D + j];                   // T words: fw[(j - D) + D], rw[j + D]
             fl[i] = fw[D + j];                                  // lo words: forward = the word ending at base j,
-#ifdef NTK_ABL_HALFIMPORTS
-            if (j - D < -1 && (j & 1)) { rl[i] = rw[16 + j]; continue; }
-#endif
             rl[i] = j - D >= -1 ? rw[j] : xl.prev(kSlotRw + 16 + j - D, rw[16 + j]);   // reverse complement = rw[(j - D) + D]: own word, r1, or the previous lane's word 16 + (j - D)
         }
         if constexpr (LIGHT)

@@ -3,6 +3,7 @@ say so in its clobber list; the same for VCC.  (2) Round 6: every statement that
 `s_mov_b64 exec, -1`) and is a memory barrier for the compiler ("memory": it holds LDS atomics the compiler cannot see, and code moved across
 a narrowed exec mask would run on a subset of the lanes).  (3) Round 6: a kernel whose asm statements issue LDS operations waits for them
 (`s_waitcnt lgkmcnt(0)`, by hand: the compiler does not count what it cannot see) after its tile loop and before it reads the histogram.
+(4) No macro of a product source has two live definitions: the rules above expand the region macros as the compiler would, which needs one text.
 Each rule comes with a test that the checker FAILS on a deliberately broken copy.  Rule (1):  (An `s_and_b64 exec, A, B` inside a masked region overwrites SCC; without the clobber the compiler is free to
 keep a 64-bit add's carry live across the region - `s_add_u32` before it, `s_addc_u32` after it - and the tile offset goes wrong for every
 wave that runs more than one tile.  That happened once, in round 5, and only a forced few-block launch in the fuzz saw it.)"""
@@ -35,9 +36,8 @@ def test_asm_blocks_that_write_scc_say_so():
     seen = 0
     for path in SRC:
         text = open(path).read()
-        macros = dict(re.findall(r"#define\s+(NTK_\w+)(?:\([^)]*\))?\s+((?:.*\\\n)*.*)", text))
         for stmt, line in asm_statements(text):
-            body = stmt
+            body, macros = stmt, macro_table(text, line)
             for _ in range(3):   # expand the region macros used inside the statement (they hold the s_and_b64 / s_bcnt1 / s_add_u32)
                 for name, val in macros.items():
                     if name in body:
@@ -64,10 +64,26 @@ MNEMONIC = re.compile(r"\b((?:s|v|ds|buffer)_[a-z0-9_]+)\b")
 EXEC_WRITE = re.compile(r"\bs_(?:and|or|xor|andn2|mov|not)\w*_b64\s+exec\b|\bs_\w+_saveexec_b64\b|\bv_cmpx_")
 
 
-def macro_table(text):
-    """name -> body of every NTK_* function-like or object-like macro; of several definitions (#ifdef ablation / #else product) the LAST one
-    is the product's (the ablation branch comes first in every such pair of ntk_kernels.hpp)."""
-    return dict(re.findall(r"#define\s+(NTK_\w+)(?:\([^)]*\))?\s+((?:.*\\\n)*.*)", text))
+MACRO_DIRECTIVE = re.compile(r"^[ \t]*#[ \t]*(define|undef)[ \t]+(NTK_\w+)(?:\([^)]*\))?[ \t]*((?:.*\\\n)*.*)", re.M)
+TWO_FACED = {"NTK_HD"}   # the function qualifier of ntk_tile.hpp: one definition for hipcc, one for the host emulation; no asm statement uses it
+
+
+def macro_table(text, line=None):
+    """name -> body of the NTK_* function-like or object-like macros that are defined at `line` (default: the end of the text), #undef
+    honoured.  A macro has ONE text: a #define that meets a live definition of the same name (an #ifdef / #else pair of variants, say) is
+    an error, for the checks below could not tell which of the two the compiler sees.  The limit: conditionals are not evaluated, the
+    directives are taken in file order - a pair written #ifdef A / #define X / #undef X / #else / #define X would pass."""
+    live = {}
+    for m in MACRO_DIRECTIVE.finditer(text):
+        if line is not None and text.count("\n", 0, m.start()) + 1 >= line:
+            break
+        kind, name, body = m.groups()
+        if kind == "undef":
+            live.pop(name, None)
+        else:
+            assert name not in live or name in TWO_FACED, f"line {text.count(chr(10), 0, m.start()) + 1}: {name} is defined twice"
+            live[name] = body
+    return live
 
 
 def expand_in_place(stmt, macros, depth=8):
@@ -94,9 +110,9 @@ def instruction_strings(expanded):
 
 def check_exec_regions(text, name="source"):
     """Rule (2).  Returns the number of exec-writing statements seen; raises AssertionError on a violation."""
-    macros = macro_table(text)
     seen = 0
     for stmt, line in asm_statements(text):
+        macros = macro_table(text, line)
         body = instruction_strings(expand_in_place(stmt, macros))
         if not EXEC_WRITE.search(body):
             continue
@@ -125,7 +141,9 @@ def check_lds_waits(text, name="source"):
     """Rule (3).  A kernel that reaches inline-asm LDS operations (directly or through the region emitters of DevMasks2 / DevMinSink) must
     hold `s_waitcnt lgkmcnt(0)` in an asm statement of its own after the tile loop (the last `next = ...readfirstlane(next)` of the pull
     loop) and before the first READ of its LDS histogram.  Returns how many kernels the rule applied to."""
-    macros = macro_table(text)
+    def has_lds_asm(body, start):   # `body` begins at offset `start` of the text
+        first = text.count("\n", 0, start)
+        return any("ds_" in instruction_strings(expand_in_place(st, macro_table(text, first + line))) for st, line in asm_statements(body))
     emitters = set()   # struct / function names whose bodies hold asm with ds_ instructions
     for m in re.finditer(r"\bstruct\s+(\w+)\s*\{", text):
         i = m.end()
@@ -134,11 +152,11 @@ def check_lds_waits(text, name="source"):
             depth += {"{": 1, "}": -1}.get(text[j], 0)
             j += 1
         body = text[i:j]
-        if any("ds_" in instruction_strings(expand_in_place(st, macros)) for st, _ in asm_statements(body)):
+        if has_lds_asm(body, i):
             emitters.add(m.group(1))
     applied = 0
     for kname, body in kernel_bodies(text):
-        own = any("ds_" in instruction_strings(expand_in_place(st, macros)) for st, _ in asm_statements(body))
+        own = has_lds_asm(body, text.index(body))
         if not own and not any(re.search(r"\b" + e + r"\b", body) for e in emitters):
             continue
         applied += 1
@@ -149,6 +167,20 @@ def check_lds_waits(text, name="source"):
         assert wait, f"{name}: {kname}: no s_waitcnt lgkmcnt(0) after the tile loop (the asm regions' LDS atomics are invisible to the compiler)"
         assert read is None or wait.start() < read.start(), f"{name}: {kname}: the LDS histogram is read before the hand-written wait"
     return applied
+
+
+def test_no_macro_has_two_live_definitions():
+    for path in SRC:
+        macro_table(open(path).read())   # (asserts)
+    pair = '#ifdef VARIANT\n#define NTK_T_EXEC(i) ""\n#else\n#define NTK_T_EXEC(i) "s_and_b64 exec, %0, %1\\n"\n#endif\n'
+    try:
+        macro_table(pair)
+    except AssertionError:
+        pass
+    else:
+        raise AssertionError("the checker accepted a macro with two definitions")
+    assert "NTK_T_EXEC" in macro_table(pair.replace("#else\n", "#else\n#undef NTK_T_EXEC\n"))   # redefined after #undef: one live text
+    assert macro_table('#define NTK_T_A 1\nasm("x");\n#undef NTK_T_A\n', 2) == {"NTK_T_A": "1"} and macro_table('#define NTK_T_A 1\n#undef NTK_T_A\n') == {}
 
 
 def test_exec_regions_restore_exec_and_clobber_memory():

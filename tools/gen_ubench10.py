@@ -10,8 +10,8 @@ K = 21
 asm_path = '/tmp/isa/k.s'
 if not os.path.exists(asm_path):
     os.makedirs('/tmp/isa', exist_ok=True)
-    subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-DNTK_KB_FIX', '-DNTK_KB_SV', '-DNTK_KB_SV2', '-DNTK_KB_HB=14', '-mllvm',
-                           '-amdgpu-sched-strategy=iterative-ilp', '-S', '--cuda-device-only', '-o', asm_path, os.path.join(here, 'kbench.hip')], stderr=subprocess.DEVNULL)
+    subprocess.check_call(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-I' + os.path.join(root, 'needletail_amd', 'csrc'), '-DNTK_KB_FIX', '-DNTK_KB_SV', '-DNTK_KB_SV2', '-DNTK_KB_HB=14', '-mllvm',
+                           '-amdgpu-sched-strategy=iterative-ilp', '-S', '--cuda-device-only', '-o', asm_path, os.path.join(here, 'kbench.hip')])
 text = open(asm_path).read()
 name = f'_ZN3ntk12scan2_kernelILi{K}ELb1ELb1ELb0ELi14ELi0ELb0EEEvNS_8ScanArgsE'
 body = text[text.index(name + ':'):]

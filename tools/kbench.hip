@@ -1,6 +1,7 @@
 // kbench.hip — standalone A/B harness for the scan kernel (no python/torch): generates the bench workload in HBM,
 // times scan_kernel<2,canon,tie_rc,accept_u,reduce> with hipEvents and prints the reduced result so that variants
-// (built with different -D NTK_V_* toggles / compiler flags) can be compared for speed AND equality.
+// (built with different -D switches / compiler flags) can be compared for speed AND equality.  The ablation switches (NTK_ABL_*, NTK_V_CLOCKS)
+// live in tools/kbench_ablations.patch; tools/build_kbench.sh applies it to a copy of the kernel headers and puts that copy on the include path.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -8,8 +9,8 @@
 #include <vector>
 #include <algorithm>
 
-#include "../needletail_amd/csrc/ntk_kernels.hpp"
-#include "../needletail_amd/csrc/ntk_plan.hpp"
+#include "ntk_kernels.hpp"
+#include "ntk_plan.hpp"
 
 using namespace ntk;
 #define CHK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
@@ -60,11 +61,13 @@ int main(int argc, char **argv)
 #ifndef NTK_KB_HB
 #define NTK_KB_HB 12
 #endif
+#ifndef NTK_ABL_FLOOR   // the floor branch runs the canonical tile body (K >= 17) whatever the build: it has no forward-only form
         static const bool kb_fwd = getenv("KB_FWD") != nullptr;   // the forward-only builds (BitNuclKmer, canonical = false)
         if (kb_fwd && k == 21) hipLaunchKernelGGL((scan2_kernel<21, false, false, false, NTK_KB_HB, 0, true>), dim3(blocks), dim3(threads), 0, 0, a);
         else if (kb_fwd && k == 31) hipLaunchKernelGGL((scan2_kernel<31, false, false, false, NTK_KB_HB, 0, true>), dim3(blocks), dim3(threads), 0, 0, a);
         else if (kb_fwd && k == 16) hipLaunchKernelGGL((scan2_kernel<16, false, false, false, NTK_KB_HB, 0, true>), dim3(blocks), dim3(threads), 0, 0, a);
         else
+#endif
         if (k == 21) hipLaunchKernelGGL((scan2_kernel<21, true, true, false, NTK_KB_HB>), dim3(blocks), dim3(threads), 0, 0, a);
         else if (k == 31) hipLaunchKernelGGL((scan2_kernel<31, true, true, false, NTK_KB_HB>), dim3(blocks), dim3(threads), 0, 0, a);
         else if (k == 23) hipLaunchKernelGGL((scan2_kernel<23, true, true, false, NTK_KB_HB>), dim3(blocks), dim3(threads), 0, 0, a);

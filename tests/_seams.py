@@ -6,7 +6,7 @@ conditions, the emulator sweeps) and the device sweeps:
   min_stride, min_seam_inputs, thin_far, minimizer_model;
 - k = 33..255 (test_wide_seams_emu.py, test_gpu_wide_seams.py): wide_input, WIDE_SEAMS, wide_reference, wide_tie_insert;
 - the lower-case watch of the speculative routes (test_lower_watch_inputs.py, test_gpu_lower_watch.py): lower_watch_input,
-  lower_watch_positions.
+  lower_watch_positions, lower_tail_lengths.
 
 Every geometry here is a restatement the tests hold the library to; none is read from the library."""
 from concurrent.futures import ThreadPoolExecutor
@@ -297,6 +297,17 @@ def lower_watch_input(k: int, seed: int = 0) -> np.ndarray:
     for frac, ch in ((0.21, b"N"), (0.43, b"\n"), (0.58, b"N"), (0.77, b"\n"), (0.9, b"N")):
         a[int(frac * len(a))] = ch[0]
     return a
+
+
+LOWER_TAIL_OFFSETS = (3, 4, 5, 14, 15, 16)
+
+
+def lower_tail_lengths(n: int):
+    """(offset, n') for the longest n' <= n whose last byte lies at offset 3, 4, 5, 14, 15 and 16 (byte 0 of a line of its own) of its
+    16-byte line: the last line then holds 4, 5, 6, 15, 16 bytes and 1 byte of input - a dword that is exactly full, one byte more, a line
+    with one byte of padding, a full line.  Behind byte n' the padding is lower case (the caller's fill): it is nobody's base and must not
+    be watched, while the last byte itself must (the mutation audit's or_of_input_bytes findings, profiles/mutation_audit/README.md)."""
+    return [(off, n - ((n - 1 - off) % 16)) for off in LOWER_TAIL_OFFSETS]
 
 
 def lower_watch_positions(n: int, seams, near=(40, 24), ends: int = 48, step: int = 16):

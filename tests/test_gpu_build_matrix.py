@@ -17,6 +17,7 @@ import oracle as O  # noqa: E402  (the checker)
 from needletail_amd import _lib as NL  # noqa: E402
 
 import _builds as B  # noqa: E402
+from _mutant_inputs import SCAN_STRIDE, pack16, tail_input  # noqa: E402
 
 GEOMETRIES = ((0, 0), (7, 0))   # the library's grid, and a few-block launch (every block pulls many tiles)
 CUTOFF = 53                     # Phred+33 Q20: the seeded qualities sit on both sides of it
@@ -398,3 +399,29 @@ def test_materialize_exact_sizes_and_flags_only(ctx, data, n):
         assert np.array_equal(gv, ev) and np.array_equal(gr[ev], er[ev]) and np.array_equal(gvals[ev], evals[ev]), (n, k, path)
         fv, fr, _, fw16, fr16 = _materialize(ctx, data.dev[False], n, k, path, pre, with_values=False)
         assert np.array_equal(fw16, w16) and np.array_equal(fr16, r16), (n, k, path, "flags only")
+
+
+@pytest.mark.parametrize("k", [5, 16, 21, 22, 32])
+def test_materialize_ignores_a_base_in_the_padding(ctx, k):
+    """lane_tile's tail rule on the device, where it shows: a last 16-byte line of 15 input bytes with an 'A' behind them
+    (tests/_mutant_inputs.py), materialised.  MaterializeSink::end_tile stores valid16 = ~inval as lane_tile leaves it, unclipped, so bit 0 of
+    the last word is position n: were the line taken whole (keep >= 15 for keep >= 16), that bit would be set - nothing else differs, and no
+    reduction over the planes reads it (window_min_reduce_kernel stops at n).  The whole valid16 and rc16 planes, that word included, and the
+    values on valid positions against the oracle; k = 21 on the canonical paths is the k-specialised build."""
+    ctx.set_launch(0, 0)
+    buf = tail_input(SCAN_STRIDE)
+    n = len(buf)
+    assert n % 16 == 15 and n > SCAN_STRIDE
+    dev = to_dev(buf)   # 'A' behind byte n
+    for path, pre in ((B.PATH_BYTES_CANONICAL, B.PRE_NORMALIZE), (B.PATH_BITS_CANONICAL, B.PRE_NONE), (B.PATH_BITS, B.PRE_NONE)):
+        m = B.resolve_mode(k, path, pre)
+        syms = B.kernels(B.Call("materialize", k, 0, path, pre, False, 0))
+        assert syms == (B.pick_scan_materialize(m, k, False),) and B.family(syms[0]) == "scan_kernel", syms
+        assert ("21, false>" in syms[0]) == (k == 21 and m.canon), syms
+        ev, er, evals = expected_planes(buf, k, path, pre)
+        assert ev[n - 1] and expected_planes(buf + b"A", k, path, pre)[0][n]   # not vacuous: the reading that takes the byte emits there
+        gv, gr, gvals, v16, r16 = _materialize(ctx, dev, n, k, path, pre)
+        assert v16[-1] & 1 == 0, ("the window ending on the padding byte is marked valid", k, path, hex(v16[-1]))
+        assert np.array_equal(v16, pack16(ev)), (k, path, "valid16", np.flatnonzero(v16 != pack16(ev))[:8])
+        assert np.array_equal(r16, pack16(er & ev)), (k, path, "rc16")
+        assert np.array_equal(gvals[ev], evals[ev]), (k, path, "values")

@@ -19,7 +19,8 @@ import oracle as O  # noqa: E402  (the checker)
 from needletail_amd import _lib as NL  # noqa: E402
 
 import _builds as B  # noqa: E402
-from _seams import LOWER_KS, WIDE_N, WK_ROW, WK_TILE, WK_WAVE, lower_watch_input, lower_watch_positions, stride_of, wide_input  # noqa: E402
+from _seams import (LOWER_KS, WIDE_N, WK_ROW, WK_TILE, WK_WAVE, lower_tail_lengths, lower_watch_input, lower_watch_positions, stride_of,  # noqa: E402
+                    wide_input)
 
 CUTOFF = 53
 PATH, PRE = B.PATH_BYTES_CANONICAL, B.PRE_NONE
@@ -183,6 +184,34 @@ def test_one_lower_case_base_is_seen_by_the_wide_pair(ctx, k):
 @pytest.mark.parametrize("k", [40, 255])
 def test_one_lower_case_base_under_a_quality_stream_wide_pair(ctx, k):
     sweep_quality(ctx, wide_input(), k, WIDE_POSITIONS)
+
+
+@pytest.mark.parametrize("k", [16, 21, 40])
+def test_last_line_padding_is_not_watched(ctx, k):
+    """The input ends with its last byte at offset 3, 4, 5, 14, 15 and 16 of its 16-byte line (lower_tail_lengths), lower-case bytes behind
+    it: all upper case counts no redone launch - the padding is nobody's base, whichever dword of the line it shares with input bytes - and
+    with the last byte lower case exactly one.  (The mutation audit's two or_of_input_bytes edits - a dword of exactly four input bytes
+    masked to none, a line of 15 input bytes taken whole - passed every sweep before these lengths; profiles/mutation_audit/README.md.)"""
+    a = lower_watch_input(k) if k <= 32 else wide_input()
+    assert_speculative(k, False)
+    t = to_dev(a, 0x61)
+    seq = t[LEAD:]
+    with redone_launches(ctx) as rl:
+        for off, n in lower_tail_lengths(len(a)):
+            head = a[:n]
+            seq[n:len(a)] = 0x61   # what lay behind byte n is padding now
+            ctx.reduce_device(seq, n, k, PATH, PRE, reset=True)
+            assert_stats_equal(ctx.accum_read(), reference(head.tobytes(), k), (k, "all upper case, last byte at offset", off))
+            assert rl.count() == 0, (k, "all upper case, last byte at offset", off)
+            b = head.copy()
+            if b[n - 1] not in b"ACGT":
+                b[n - 1] = ord("A")
+            b[n - 1] |= 0x20
+            seq[n - 1] = int(b[n - 1])
+            ctx.reduce_device(seq, n, k, PATH, PRE, reset=True)
+            assert_stats_equal(ctx.accum_read(), reference(b.tobytes(), k), (k, "last byte lower case at offset", off))
+            assert rl.count() == 1, (k, "last byte lower case at offset", off)
+            seq[:len(a)] = torch.from_numpy(a.copy()).cuda()
 
 
 @pytest.mark.parametrize("k", [16, 21, 24, 40])

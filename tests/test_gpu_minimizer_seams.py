@@ -27,6 +27,7 @@ from needletail_amd import _lib as NL  # noqa: E402
 import _builds as B  # noqa: E402
 from _seams import (ACGT, FUSED_PAIRS, FUSED_Q_PAIRS, GENERIC_PAIRS, TWO_PASS_PAIRS, TWO_PASS_SEAMS, map_threads, min_seam_inputs,  # noqa: E402
                     min_stride, thin_far, tie_insert, two_pass_inputs)
+from _mutant_inputs import SCAN_STRIDE, palindrome_kmer_inputs, tail_input  # noqa: E402
 
 CUTOFF = 53
 MAX_CASES = 1500
@@ -194,6 +195,51 @@ def test_two_pass_only_pair(ctx, k, w, seams):
     assert ctx.get_option(NL.OPT_MINIMIZER_CHUNK_BYTES) > len(cases[0][1]) > 4096   # by default one chunk, with the option two
     runs = [("two_pass", 0, (BYTE_PATH,), 0), ("two_pass", 0, (BYTE_PATH,), 4096)]
     run_cases(ctx, k, w, cases, wants_of(cases, k, w, (BYTE_PATH,)), runs, 992)
+
+
+# ---- the inputs added for the survivors of the mutation audit (tests/_mutant_inputs.py, profiles/mutation_audit/README.md) -----------------
+
+def check_on_route(ctx, buf, k, w, route, extra, paths, what):
+    """One input through one forced route, both paths, against the literal minimizer of every window; to_dev pads with 'A'."""
+    t = to_dev(buf)
+    for path in paths:
+        assert_route(k, w, path, route, extra, False)
+    with ctx_option(ctx, NL.OPT_MINIMIZER_ROUTE, ROUTE_BITS[route] | extra):
+        for path in paths:
+            ctx.reduce_device(t, len(buf), k, path[1], path[2], w=w, reset=True)
+            want = O.minimizers_reduce(buf, k, w, accept_u=path[3][0], tie_rc=path[3][1])
+            assert_stats_equal(ctx.accum_read(), want, (what, k, w, route, extra, path[0]))
+
+
+@pytest.mark.parametrize("k", [5, 16, 22, 32])
+def test_scan_kernel_ignores_a_base_in_the_padding(ctx, k):
+    """The two-pass route with w = 1 (every k-mer is its window's minimizer) on a last 16-byte line of 15 input bytes with an 'A' behind them:
+    what scan_kernel materialises for the line and what window_min_reduce_kernel takes from it.  The reduce stops at byte n whatever the
+    scan marked valid behind it, so this holds the pair and not lane_tile's tail rule alone; the rule itself shows in the materialised
+    valid16 word, test_gpu_build_matrix.py::test_materialize_ignores_a_base_in_the_padding."""
+    ctx.set_launch(0, 0)
+    buf = tail_input(SCAN_STRIDE)
+    assert len(buf) % 16 == 15
+    check_on_route(ctx, buf, k, 1, "two_pass", 0, (BYTE_PATH, BIT_PATH), "a base in the padding")
+
+
+@pytest.mark.parametrize("k,w", [(21, 11), (24, 11), (26, 18), (11, 49)])
+def test_generic_kernel_ignores_a_base_in_the_padding(ctx, k, w):
+    """minimizer_invalid16's tail rule, both smear forms and both key forms."""
+    ctx.set_launch(0, 0)
+    buf = tail_input(min_stride(k, w, "generic"))
+    assert len(buf) % 16 == 15
+    for extra in ((0, NL.ROUTE_NO_F64) if k <= 25 else (0,)):
+        check_on_route(ctx, buf, k, w, "generic", extra, (BYTE_PATH, BIT_PATH), "a base in the padding")
+
+
+@pytest.mark.parametrize("k", [18, 22, 32, 4, 16])
+def test_scan_kernel_reports_a_self_palindrome_by_the_paths_tie_rule(ctx, k):
+    """lane_tile's strand compare on a k-mer equal to its own reverse complement (the byte path reports rc, the bit path forward), ending
+    mid-tile, on both sides of the 992-byte seam and of a lane boundary: scan_kernel through the two-pass route with w = 1."""
+    ctx.set_launch(0, 0)
+    for e, buf in palindrome_kmer_inputs(k):
+        check_on_route(ctx, buf, k, 1, "two_pass", 0, (BYTE_PATH, BIT_PATH), ("self-palindrome ending at", e))
 
 
 # ---- launch shape ----------------------------------------------------------------------------------------------------------------------

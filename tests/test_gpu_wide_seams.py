@@ -20,6 +20,7 @@ from needletail_amd import _lib as NL  # noqa: E402
 
 import _builds as B  # noqa: E402
 from _seams import (WIDE_KS, WIDE_N, WIDE_TIE_KS, wide_break_offsets, wide_input, wide_reference, wide_tie_insert, wide_tie_starts)  # noqa: E402
+from _mutant_inputs import WIDE_TILE, tail_input  # noqa: E402
 
 PRES = ((B.PRE_NORMALIZE, "normalised"), (B.PRE_NONE, "raw"))
 # canonical_bytes_reduce_kernel (ntk_kernels.hpp): 256 threads (kPlThreads) walk PER = 32 window starts each, a block's tile is 8192 bytes
@@ -115,6 +116,26 @@ def test_breaks_around_row_wave_and_tile_seams(ctx, k):
         call = B.Call("reduce", k, 0, B.PATH_BYTES_CANONICAL, pre, False, 0)
         assert B.kernels(call) == (B.wide_reduce(pre >= B.PRE_NORMALIZE, False), B.bytes_reduce(True, False))
     break_sweep(ctx, k, wide_break_offsets(k), 0, "speculative route")
+
+
+@pytest.mark.parametrize("k", [33, 64, 255])
+def test_a_base_in_the_padding_is_ignored(ctx, k):
+    """wk_stage_slot's tail rule on the device (tests/_mutant_inputs.py tail_input, added for a survivor of the mutation audit): the last
+    16-byte line holds 15 input bytes and an 'A' behind them; were the line taken whole, one window more would be emitted.  The
+    packed-stream kernel's own result: nothing is redone."""
+    ctx.set_launch(0, 0)
+    buf = tail_input(WIDE_TILE + 256)
+    assert len(buf) % 16 == 15 and wide_reference(buf + b"A", k)["n_total"] == wide_reference(buf, k)["n_total"] + 1
+    t = to_dev(buf)
+    want = wide_reference(buf, k)
+    with redone_launches(ctx) as rl:
+        for pre, pname in PRES:
+            call = B.Call("reduce", k, 0, B.PATH_BYTES_CANONICAL, pre, False, 0)
+            assert B.kernels(call) == (B.wide_reduce(pre >= B.PRE_NORMALIZE, False), B.bytes_reduce(True, False))
+            ctx.reduce_device(t, len(buf), k, B.PATH_BYTES_CANONICAL, pre, reset=True)
+            got = ctx.accum_read()
+            assert_stats_equal(got, want, ("a base in the padding", k, pname))
+            assert got["n_undigested"] == got["n_total"] and rl.count() == 0, (k, pname)
 
 
 def test_breaks_on_the_direct_route(ctx):

@@ -7,7 +7,8 @@ import pytest
 
 import oracle as O
 
-from _seams import LOWER_KS, WIDE_N, WK_ROW, WK_TILE, WK_WAVE, lower_watch_input, lower_watch_positions, stride_of, wide_input
+from _seams import (LOWER_KS, LOWER_TAIL_OFFSETS, WIDE_N, WK_ROW, WK_TILE, WK_WAVE, lower_tail_lengths, lower_watch_input, lower_watch_positions,
+                    stride_of, wide_input)
 
 PATH_BYTES_CANONICAL, PRE_NONE = 0, 0   # include/needletail_amd.h
 
@@ -58,3 +59,13 @@ def test_wide_positions_cover_the_seams():
         assert set(range(S - 40, S + 25)) <= pos
     assert set(range(48)) | set(range(WIDE_N - 48, WIDE_N)) <= pos and len(pos) < 320
     assert not any(c & 0x20 for c in wide_input().tobytes())
+
+
+@pytest.mark.parametrize("n", [WIDE_N, 3 * 1004 - 5, 3 * 1008 - 5, 17])
+def test_tail_lengths_put_the_last_byte_where_they_say(n):
+    got = lower_tail_lengths(n)
+    assert [off for off, _ in got] == list(LOWER_TAIL_OFFSETS)
+    for off, m in got:
+        assert n - 16 < m <= n and (m - 1) % 16 == off % 16, (n, off, m)
+    # a dword exactly full / one byte more / one byte short of the line / the line full / one byte in a line of its own
+    assert sorted(m % 16 for _, m in got) == [0, 1, 4, 5, 6, 15]

@@ -122,6 +122,31 @@ class MinHashSet(L.Handle):
                 self.num, self.max_hash = min(self.num, mh.num), min(self.max_hash, mh.max_hash)
         return index.value
 
+    def add_record_sketches(self, rmh) -> range:
+        """Append every record's sketch of a RecordMinHash, in record order; returns the range of their indices.  The checks are those
+        add() makes for a KmerMinHash of the handle's k, path and kind, made before anything is added, as is the check that every
+        sketch ascends strictly.  Not atomic beyond that: if an add fails halfway (out of memory), the sketches added so far stay,
+        and k, path and kind are recorded for them."""
+        self._admit(rmh)
+        offsets, _, hashes, counts = rmh.sketches()
+        n = offsets.size - 1
+        inner = np.ones(hashes.size, dtype=bool)
+        inner[offsets[:-1][offsets[:-1] < hashes.size].astype(np.int64)] = False   # the first entry of every sketch
+        if hashes.size > 1 and not (hashes[1:] > hashes[:-1])[inner[1:]].all():
+            raise L.NtkError(2, PREFIX + "add: a record's hashes do not ascend")
+        first, added = len(self), 0
+        try:
+            for r in range(n):
+                h, c = hashes[int(offsets[r]):int(offsets[r + 1])], counts[int(offsets[r]):int(offsets[r + 1])]
+                self._check("add", self._h, _data(h), _data(c) if self.abundance else None, h.size, None)
+                added += 1
+        finally:
+            if added and self.k is None:
+                self.k, self.path, self.num, self.scaled, self.max_hash = rmh.k, rmh.path, rmh.num, rmh.scaled, rmh.max_hash
+            elif added:
+                self.num, self.max_hash = min(self.num, rmh.num), min(self.max_hash, rmh.max_hash)
+        return range(first, first + n)
+
     def __len__(self) -> int:
         return self.stats()["n_sketches"]
 

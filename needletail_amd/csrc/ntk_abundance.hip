@@ -256,35 +256,21 @@ struct ntk_read_abundance : Consumer {   // k and path: the table's
     ntk_kmer_table *table = nullptr;   // borrowed
     MaterialiseScratch scratch;        // of one chunk
     // batch-long, grown on demand
-    uint64_t batch_bytes = 0;          // bases they hold (a multiple of 16)
-    uint64_t *d_counts = nullptr;      // 8 B per base
-    uint16_t *d_plane = nullptr;       // 1/8 B per base
-    uint64_t *d_long = nullptr;        // [0]: the number of long records, then their indices (one per kLongRecord bases at most)
+    DeviceArray<uint64_t> d_counts;    // 8 B per base
+    DeviceArray<uint16_t> d_plane;     // 1/8 B per base
+    DeviceArray<uint64_t> d_long;      // [0]: the number of long records, then their indices (one per kLongRecord bases at most)
 
-    uint64_t long_cap() const { return (batch_bytes >> 16) + 1; }
+    uint64_t long_cap() const { return d_long.cap - 1; }
 
-    void release_batch()
-    {
-        for (void *q : {(void *)d_counts, (void *)d_plane, (void *)d_long})
-            if (q) (void)hipFree(q);
-        d_counts = nullptr; d_plane = nullptr; d_long = nullptr; batch_bytes = 0;
-    }
+    void release_batch() { d_counts.release(); d_plane.release(); d_long.release(); }
 
     int ensure_batch(uint64_t n_bytes)
     {
-        const uint64_t need = (n_bytes + 15) & ~(uint64_t)15;
-        if (need <= batch_bytes) return NTK_OK;
-        CT_HIPCHK(hipStreamSynchronize(stream));
-        release_batch();
-        hipError_t e;
-        if ((e = hipMalloc((void **)&d_counts, need * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_plane, need / 16 * sizeof(uint16_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_long, ((need >> 16) + 2) * sizeof(uint64_t))) != hipSuccess) {
-            release_batch();
-            return alloc_status(e);
-        }
-        batch_bytes = need;
-        return NTK_OK;
+        const uint64_t need = (n_bytes + 15) & ~(uint64_t)15;   // bases (a multiple of 16)
+        int rc = d_counts.ensure(stream, need, grow_exact);
+        if (!rc) rc = d_plane.ensure(stream, need / 16, grow_exact);
+        if (!rc) rc = d_long.ensure(stream, (need >> 16) + 2, grow_exact);
+        return rc;
     }
 };
 
@@ -338,22 +324,22 @@ int ntk_read_abundance_run_device(ntk_read_abundance *a, const uint8_t *d_seq, c
     rc = for_each_chunk(*a, a->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         // values at invalid positions are undefined: looking them up is a bounded read-only probe, and the plane drops their counts.
         // An incomplete table fails here, on the first chunk, before any row is written.  Synchronises.
-        const int rc = ntk_kmer_table_lookup_device(a->table, a->scratch.d_values + c.skip(), c.end - c.start, a->d_counts + c.start);
+        const int rc = ntk_kmer_table_lookup_device(a->table, a->scratch.d_values.p + c.skip(), c.end - c.start, a->d_counts.p + c.start);
         if (rc) return rc;
         CT_HIPCHK(hipSetDevice(a->device));
-        CT_HIPCHK(hipMemcpyAsync(a->d_plane + c.start / 16, a->scratch.d_valid16 + c.skip() / 16,
+        CT_HIPCHK(hipMemcpyAsync(a->d_plane.p + c.start / 16, a->scratch.d_valid16.p + c.skip() / 16,
                                  (c.end - c.start + 15) / 16 * sizeof(uint16_t), hipMemcpyDeviceToDevice, a->stream));
         return NTK_OK;
     });
     if (rc) return rc;
     RaArgs g;
-    g.counts = a->d_counts; g.plane = a->d_plane; g.offsets = d_offsets;
+    g.counts = a->d_counts.p; g.plane = a->d_plane.p; g.offsets = d_offsets;
     g.n_bytes = n_bytes; g.n_records = n_records;
     g.min_count = min_count ? min_count : 1;
     g.k = a->k;
-    g.n_long = a->d_long; g.long_list = a->d_long + 1; g.long_cap = a->long_cap();
+    g.n_long = a->d_long.p; g.long_list = a->d_long.p + 1; g.long_cap = a->long_cap();
     g.rows = d_rows;
-    CT_HIPCHK(hipMemsetAsync(a->d_long, 0, sizeof(uint64_t), a->stream));
+    CT_HIPCHK(hipMemsetAsync(a->d_long.p, 0, sizeof(uint64_t), a->stream));
     hipLaunchKernelGGL(ra_wave_kernel, dim3(grid_for(n_records, kWaveThreads / 64, (unsigned)a->n_cu * 8)), dim3(kWaveThreads), 0,
                        a->stream, g);
     CT_HIPCHK(hipGetLastError());

@@ -1,7 +1,7 @@
 // What every consumer of the core's public ABI shares (the two count tables through ntk_count_common.hpp, the sketch, MinHash, per-read
 // abundance and trimming directly): the hash, the wave and block sums, the launch helpers, the handle's base with the checks of a batch
-// call, the scratch of the materialise face with the walk over a batch's chunks (ntk_chunks.hpp), and the record rule of the two
-// libraries that read records.  Everything is in an anonymous namespace, so each library keeps a private copy and exports nothing new.
+// call, how a handle owns device and pinned memory (ntk_device_mem.hpp), the scratch of the materialise face with the walk over a
+// batch's chunks (ntk_chunks.hpp), and the record rule of the two libraries that read records.  Everything is in an anonymous namespace, so each library keeps a private copy and exports nothing new.
 // DESIGN.md section 16.
 #pragma once
 
@@ -18,6 +18,8 @@
             return NTK_ERR_HIP;              \
         }                                    \
     } while (0)
+
+#include "ntk_device_mem.hpp"
 
 namespace {
 
@@ -120,36 +122,34 @@ inline int check_batch_pointers(const uint8_t *d_seq, const uint8_t *d_qual)
     return !d_seq || ((uintptr_t)d_seq & 15) || ((uintptr_t)d_qual & 15) ? NTK_ERR_BAD_ARG : NTK_OK;
 }
 
+// The quality mask of a batch call, for the kernels that read the quality bytes themselves: the cutoff of the params' flags and the
+// bytes it applies to (no cutoff or no bytes: no mask).
+template <class Args>
+inline void set_quality(Args &a, const ntk_params *p, const uint8_t *d_qual)
+{
+    a.cutoff = (p->flags >> 8) & 0xFF;
+    a.qual = a.cutoff ? d_qual : nullptr;
+    if (!a.qual) a.cutoff = 0;
+}
+
 // The scratch of one chunk of the core's materialise face (values, valid plane, strand plane: 10 B per base), grown on demand.  Owned by
 // whatever consumes that face chunk by chunk.
 struct MaterialiseScratch {
-    uint64_t bytes = 0;   // bases it holds (a multiple of 16)
-    uint64_t *d_values = nullptr;
-    uint16_t *d_valid16 = nullptr, *d_rc16 = nullptr;
+    DeviceArray<uint64_t> d_values;
+    DeviceArray<uint16_t> d_valid16, d_rc16;
 
-    void release()
-    {
-        if (d_values) (void)hipFree(d_values);
-        if (d_valid16) (void)hipFree(d_valid16);
-        if (d_rc16) (void)hipFree(d_rc16);
-        d_values = nullptr; d_valid16 = d_rc16 = nullptr; bytes = 0;
-    }
+    uint64_t bytes() const { return d_rc16.cap * 16; }   // bases it holds (a multiple of 16)
+    uint64_t device_bytes() const { return d_values.bytes() + d_valid16.bytes() + d_rc16.bytes(); }
+
+    void release() { d_values.release(); d_valid16.release(); d_rc16.release(); }
 
     int ensure(hipStream_t stream, uint64_t len)
     {
         const uint64_t need = (len + 15) & ~(uint64_t)15;
-        if (need <= bytes) return NTK_OK;
-        CT_HIPCHK(hipStreamSynchronize(stream));   // the old scratch may still be read by queued kernels
-        release();
-        hipError_t e;
-        if ((e = hipMalloc((void **)&d_values, need * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_valid16, need / 16 * sizeof(uint16_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_rc16, need / 16 * sizeof(uint16_t))) != hipSuccess) {
-            release();
-            return alloc_status(e);
-        }
-        bytes = need;
-        return NTK_OK;
+        int rc = d_values.ensure(stream, need, grow_exact);
+        if (!rc) rc = d_valid16.ensure(stream, need / 16, grow_exact);
+        if (!rc) rc = d_rc16.ensure(stream, need / 16, grow_exact);
+        return rc;
     }
 };
 
@@ -163,8 +163,8 @@ int for_each_chunk(const Consumer &h, MaterialiseScratch &scratch, const uint8_t
     int rc = scratch.ensure(h.stream, chunk_scratch_bases(n_bytes, h.k));
     for (uint64_t start = 0; !rc && start < n_bytes; start += kChunkBases) {
         const Chunk c = chunk_at(n_bytes, h.k, start);
-        rc = ntk_materialize_device_quality(h.ctx, d_seq + c.base, d_qual ? d_qual + c.base : nullptr, c.len(), p, scratch.d_values,
-                                            scratch.d_valid16, scratch.d_rc16);
+        rc = ntk_materialize_device_quality(h.ctx, d_seq + c.base, d_qual ? d_qual + c.base : nullptr, c.len(), p, scratch.d_values.p,
+                                            scratch.d_valid16.p, scratch.d_rc16.p);
         if (rc) return rc;
         CT_HIPCHK(hipSetDevice(h.device));
         rc = body(c);

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kThreads) void kt_lookup_kernel(const uint64_t *key
 }  // namespace
 
 struct ntk_kmer_table : TableCore {
-    uint64_t *d_keys = nullptr;
+    DeviceArray<uint64_t> d_keys;
     MaterialiseScratch scratch;   // of one chunk (grown on demand)
 };
 
@@ -146,14 +146,15 @@ int ntk_kmer_table_create(ntk_ctx *ctx, uint32_t k, uint32_t path, uint64_t capa
 void ntk_kmer_table_destroy(ntk_kmer_table *t)
 {
     if (!t) return;
-    t->release({t->scratch.d_values, t->scratch.d_valid16, t->scratch.d_rc16, t->d_keys});   // the scratch, then the keys
+    t->release({&t->d_keys});
+    t->scratch.release();
     delete t;
 }
 
 int ntk_kmer_table_reset(ntk_kmer_table *t)
 {
     if (!t) return NTK_ERR_BAD_ARG;
-    return t->reset({t->d_keys}, kStWords);
+    return t->reset({&t->d_keys}, kStWords);
 }
 
 int ntk_kmer_table_count_device(ntk_kmer_table *t, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes, const ntk_params *p)
@@ -165,9 +166,9 @@ int ntk_kmer_table_count_device(ntk_kmer_table *t, const uint8_t *d_seq, const u
     // of every chunk only the windows ending at or after its start count
     return for_each_chunk(*t, t->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         InsertArgs a;
-        a.values = t->scratch.d_values; a.valid16 = t->scratch.d_valid16;
+        a.values = t->scratch.d_values.p; a.valid16 = t->scratch.d_valid16.p;
         a.first = c.skip(); a.n = c.len();
-        a.keys = t->d_keys; a.counts = t->d_counts; a.stats = t->d_stats;
+        a.keys = t->d_keys.p; a.counts = t->d_counts.p; a.stats = t->d_stats.p;
         a.mask = t->slots - 1; a.probe_max = t->probe_max;
         hipLaunchKernelGGL(kt_insert_kernel, dim3(grid_for(a.n - a.first, kThreads, (unsigned)t->n_cu * 8)), dim3(kThreads), 0,
                            t->stream, a);
@@ -197,7 +198,7 @@ int ntk_kmer_table_extract_device(ntk_kmer_table *t, uint64_t min_count, uint64_
     int rc = t->read_complete(w, kStWords);
     if (rc) return rc;
     if (min_count == 0) min_count = 1;
-    rc = t->extract_offsets(t->d_keys, min_count, &in_table);
+    rc = t->extract_offsets(t->d_keys.p, min_count, &in_table);
     if (rc) return rc;
     const uint64_t ones = w[kStOnes] >= min_count ? w[kStOnes] : 0, need = in_table + (ones ? 1 : 0);
     *n = need;
@@ -208,8 +209,8 @@ int ntk_kmer_table_extract_device(ntk_kmer_table *t, uint64_t min_count, uint64_
         rc = t->scatter_sort<uint64_t>(
             in_table,
             [&](uint64_t *tk, uint64_t *tc) {
-                hipLaunchKernelGGL(kt_extract_scatter_kernel, dim3((unsigned)t->extract_blocks()), dim3(kThreads), 0, t->stream, t->d_keys,
-                                   t->d_counts, t->slots, min_count, t->d_offsets, tk, tc);
+                hipLaunchKernelGGL(kt_extract_scatter_kernel, dim3((unsigned)t->extract_blocks()), dim3(kThreads), 0, t->stream, t->d_keys.p,
+                                   t->d_counts.p, t->slots, min_count, t->d_offsets.p, tk, tc);
             },
             // the keys are < 4^k: a radix sort on the low 2k bits orders them
             [&](void *tmp, size_t &tmp_bytes, uint64_t *tk, uint64_t *tc) {
@@ -218,10 +219,9 @@ int ntk_kmer_table_extract_device(ntk_kmer_table *t, uint64_t min_count, uint64_
         if (rc) return rc;
     }
     if (ones) {   // the all-ones key sorts last
-        t->h_stage[0] = kEmpty; t->h_stage[1] = ones;
-        CT_HIPCHK(hipMemcpyAsync(d_keys + in_table, t->h_stage, sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
-        CT_HIPCHK(hipMemcpyAsync(d_counts + in_table, t->h_stage + 1, sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
-        CT_HIPCHK(hipStreamSynchronize(t->stream));
+        t->h_stage.p[0] = kEmpty; t->h_stage.p[1] = ones;
+        CT_HIPCHK(hipMemcpyAsync(d_keys + in_table, t->h_stage.p, sizeof(uint64_t), hipMemcpyHostToDevice, t->stream));
+        return t->h_stage.write(t->stream, d_counts + in_table, 1, 1);
     }
     return NTK_OK;
 }
@@ -231,7 +231,7 @@ int ntk_kmer_table_spectrum(ntk_kmer_table *t, uint64_t *hist, uint32_t n_bins)
     if (!t || !hist || n_bins < 2 || n_bins > kMaxBins) return NTK_ERR_BAD_ARG;
     uint64_t w[kStWords];
     int rc = t->read_complete(w, kStWords);
-    if (!rc) rc = t->spectrum(t->d_keys, hist, n_bins);
+    if (!rc) rc = t->spectrum(t->d_keys.p, hist, n_bins);
     if (rc) return rc;
     if (w[kStOnes]) hist[w[kStOnes] < n_bins - 1 ? w[kStOnes] : n_bins - 1]++;
     return NTK_OK;
@@ -244,8 +244,8 @@ int ntk_kmer_table_lookup_device(ntk_kmer_table *t, const uint64_t *d_queries, u
     int rc = t->read_complete(w, kStWords);
     if (rc) return rc;
     if (n == 0) return NTK_OK;
-    hipLaunchKernelGGL(kt_lookup_kernel, dim3(grid_for(n, kThreads, (unsigned)t->n_cu * 8)), dim3(kThreads), 0, t->stream, t->d_keys,
-                       t->d_counts, t->slots - 1, t->probe_max, w[kStOnes], d_queries, n, d_counts);
+    hipLaunchKernelGGL(kt_lookup_kernel, dim3(grid_for(n, kThreads, (unsigned)t->n_cu * 8)), dim3(kThreads), 0, t->stream, t->d_keys.p,
+                       t->d_counts.p, t->slots - 1, t->probe_max, w[kStOnes], d_queries, n, d_counts);
     CT_HIPCHK(hipGetLastError());
     CT_HIPCHK(hipStreamSynchronize(t->stream));
     return NTK_OK;

@@ -76,12 +76,12 @@ __global__ __launch_bounds__(kThreads) void ct_spectrum_kernel(const uint64_t *o
 // The host side of a table apart from its key words, which the table adds (keys; hi, lo) and hands to the helpers that set up, clear
 // or free every slot array.  `stat_words`: the length of the table's stats array.
 struct TableCore : Consumer {
+    using KeyWords = std::initializer_list<DeviceArray<uint64_t> *>;
     uint32_t probe_max = kProbeMax;
     uint64_t slots = 0;
-    uint64_t *d_counts = nullptr;
-    uint64_t *d_stats = nullptr, *d_hist = nullptr, *d_offsets = nullptr;
-    uint32_t *d_block_counts = nullptr;
-    uint64_t *h_stage = nullptr;   // pinned: stats and spectrum read-backs
+    DeviceArray<uint64_t> d_counts, d_stats, d_hist, d_offsets;
+    DeviceArray<uint32_t> d_block_counts;
+    Pinned<uint64_t> h_stage;   // stats and spectrum read-backs
 
     uint64_t extract_blocks() const { return (slots + kExtractPerBlock - 1) / kExtractPerBlock; }
 
@@ -95,42 +95,37 @@ struct TableCore : Consumer {
     }
 
     // the key words (one u64 per slot each), then the counts and the buffers of stats, extract and spectrum
-    int alloc(std::initializer_list<uint64_t **> key_words, int stat_words)
+    int alloc(KeyWords key_words, int stat_words)
     {
-        hipError_t e;
-        for (uint64_t **w : key_words)
-            if ((e = hipMalloc((void **)w, slots * sizeof(uint64_t))) != hipSuccess) return alloc_status(e);
+        int rc = NTK_OK;
+        for (DeviceArray<uint64_t> *w : key_words)
+            if ((rc = w->ensure(stream, slots, grow_exact))) return rc;
         const uint64_t nb = extract_blocks();
-        if ((e = hipMalloc((void **)&d_counts, slots * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_stats, stat_words * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_hist, kMaxBins * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_offsets, (nb + 1) * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&d_block_counts, nb * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipHostMalloc((void **)&h_stage, kMaxBins * sizeof(uint64_t), hipHostMallocDefault)) != hipSuccess)
-            return alloc_status(e);
-        return NTK_OK;
+        if ((rc = d_counts.ensure(stream, slots, grow_exact)) || (rc = d_stats.ensure(stream, stat_words, grow_exact)) ||
+            (rc = d_hist.ensure(stream, kMaxBins, grow_exact)) || (rc = d_offsets.ensure(stream, nb + 1, grow_exact)) ||
+            (rc = d_block_counts.ensure(stream, nb, grow_exact)))
+            return rc;
+        return h_stage.alloc(kMaxBins);
     }
 
     // queued: every key word EMPTY, the counts and stats 0
-    int reset(std::initializer_list<uint64_t *> key_words, int stat_words)
+    int reset(KeyWords key_words, int stat_words)
     {
         CT_HIPCHK(hipSetDevice(device));
-        for (uint64_t *w : key_words) CT_HIPCHK(hipMemsetAsync(w, 0xFF, slots * sizeof(uint64_t), stream));
-        CT_HIPCHK(hipMemsetAsync(d_counts, 0, slots * sizeof(uint64_t), stream));
-        CT_HIPCHK(hipMemsetAsync(d_stats, 0, stat_words * sizeof(uint64_t), stream));
+        for (DeviceArray<uint64_t> *w : key_words) CT_HIPCHK(hipMemsetAsync(w->p, 0xFF, slots * sizeof(uint64_t), stream));
+        CT_HIPCHK(hipMemsetAsync(d_counts.p, 0, slots * sizeof(uint64_t), stream));
+        CT_HIPCHK(hipMemsetAsync(d_stats.p, 0, stat_words * sizeof(uint64_t), stream));
         return NTK_OK;
     }
 
-    // once the stream is idle: the table's own device buffers (`own`, in order), then the core's; errors are dropped
-    void release(std::initializer_list<void *> own)
+    // once the stream is idle: the table's key words, then the core's buffers; errors are dropped
+    void release(KeyWords key_words)
     {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
-        for (void *p : own)
-            if (p) (void)hipFree(p);
-        for (void *p : {(void *)d_counts, (void *)d_stats, (void *)d_hist, (void *)d_offsets, (void *)d_block_counts})
-            if (p) (void)hipFree(p);
-        if (h_stage) (void)hipHostFree(h_stage);
+        for (DeviceArray<uint64_t> *w : key_words) w->release();
+        d_counts.release(); d_stats.release(); d_hist.release(); d_offsets.release(); d_block_counts.release();
+        h_stage.release();
         (void)hipGetLastError();
     }
 
@@ -138,10 +133,9 @@ struct TableCore : Consumer {
     int read_stats(uint64_t *w, int stat_words)
     {
         CT_HIPCHK(hipSetDevice(device));
-        CT_HIPCHK(hipMemcpyAsync(h_stage, d_stats, stat_words * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        CT_HIPCHK(hipStreamSynchronize(stream));
-        memcpy(w, h_stage, stat_words * sizeof(uint64_t));
-        return NTK_OK;
+        const int rc = h_stage.read(stream, d_stats.p, stat_words);
+        if (!rc) memcpy(w, h_stage.p, stat_words * sizeof(uint64_t));
+        return rc;
     }
 
     // read_stats for the read side, which refuses an incomplete table: NTK_ERR_CAPACITY once anything was dropped
@@ -156,58 +150,50 @@ struct TableCore : Consumer {
     int extract_offsets(const uint64_t *occ, uint64_t min_count, uint64_t *total)
     {
         const uint64_t nb = extract_blocks();
-        hipLaunchKernelGGL(ct_extract_count_kernel, dim3((unsigned)nb), dim3(kThreads), 0, stream, occ, d_counts, slots, min_count,
-                           d_block_counts);
+        hipLaunchKernelGGL(ct_extract_count_kernel, dim3((unsigned)nb), dim3(kThreads), 0, stream, occ, d_counts.p, slots, min_count,
+                           d_block_counts.p);
         CT_HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(ct_extract_scan_kernel, dim3(1), dim3(1024), 0, stream, d_block_counts, (uint32_t)nb, d_offsets);
+        hipLaunchKernelGGL(ct_extract_scan_kernel, dim3(1), dim3(1024), 0, stream, d_block_counts.p, (uint32_t)nb, d_offsets.p);
         CT_HIPCHK(hipGetLastError());
-        CT_HIPCHK(hipMemcpyAsync(h_stage, d_offsets + nb, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        CT_HIPCHK(hipStreamSynchronize(stream));
-        *total = h_stage[0];
-        return NTK_OK;
+        const int rc = h_stage.read(stream, d_offsets.p + nb, 1);
+        if (!rc) *total = h_stage.p[0];
+        return rc;
     }
 
-    // extract, step 3 and the sort, on n > 0 pairs in buffers allocated for the call: scatter(tk, tc) queues the table's scatter
+    // extract, step 3 and the sort, on n > 0 pairs in arrays allocated for the call: scatter(tk, tc) queues the table's scatter
     // kernel into them, sort(tmp, tmp_bytes, tk, tc) its rocprim::radix_sort_pairs into the caller's arrays (tmp = nullptr: the size
-    // query).  Synchronises, then frees the buffers.
+    // query).  Synchronises, then frees the arrays: a table is large, and this memory goes back at once.
     template <class Key, class Scatter, class Sort>
     int scatter_sort(uint64_t n, Scatter scatter, Sort sort)
     {
-        Key *tk = nullptr;
-        uint64_t *tc = nullptr;
-        void *tmp = nullptr;
-        size_t tmp_bytes = 0;
-        int rc = NTK_OK;
-        hipError_t e;
-        if ((e = hipMalloc((void **)&tk, n * sizeof(Key))) != hipSuccess ||
-            (e = hipMalloc((void **)&tc, n * sizeof(uint64_t))) != hipSuccess ||
-            (e = sort(nullptr, tmp_bytes, tk, tc)) != hipSuccess ||
-            (e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1)) != hipSuccess) {
-            rc = alloc_status(e);
-        } else {
-            scatter(tk, tc);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = sort(tmp, tmp_bytes, tk, tc);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) { (void)hipGetLastError(); rc = NTK_ERR_HIP; }
+        DeviceArray<Key> tk;
+        DeviceArray<uint64_t> tc;
+        DeviceArray<char> tmp;
+        int rc = tk.ensure(stream, n, grow_exact);
+        if (!rc) rc = tc.ensure(stream, n, grow_exact);
+        if (!rc) {
+            scatter(tk.p, tc.p);
+            if (hipGetLastError() != hipSuccess) rc = NTK_ERR_HIP;
         }
-        (void)hipStreamSynchronize(stream);
-        for (void *q : {(void *)tk, (void *)tc, tmp})
-            if (q) (void)hipFree(q);
+        if (!rc) rc = with_tmp(tmp, stream, grow_exact, [&](void *t, size_t &t_bytes) { return sort(t, t_bytes, tk.p, tc.p); });
+        if (hipStreamSynchronize(stream) != hipSuccess) {
+            (void)hipGetLastError();
+            if (!rc) rc = NTK_ERR_HIP;
+        }
+        tk.release(); tc.release(); tmp.release();
         return rc;
     }
 
     // the spectrum of the occupied slots into hist[0, n_bins) (synchronises)
     int spectrum(const uint64_t *occ, uint64_t *hist, uint32_t n_bins)
     {
-        CT_HIPCHK(hipMemsetAsync(d_hist, 0, n_bins * sizeof(uint64_t), stream));
+        CT_HIPCHK(hipMemsetAsync(d_hist.p, 0, n_bins * sizeof(uint64_t), stream));
         hipLaunchKernelGGL(ct_spectrum_kernel, dim3(grid_for(slots, kThreads, (unsigned)n_cu * 2)), dim3(kThreads),
-                           n_bins * sizeof(uint32_t), stream, occ, d_counts, slots, n_bins, d_hist);
+                           n_bins * sizeof(uint32_t), stream, occ, d_counts.p, slots, n_bins, d_hist.p);
         CT_HIPCHK(hipGetLastError());
-        CT_HIPCHK(hipMemcpyAsync(h_stage, d_hist, n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        CT_HIPCHK(hipStreamSynchronize(stream));
-        memcpy(hist, h_stage, n_bins * sizeof(uint64_t));
-        return NTK_OK;
+        const int rc = h_stage.read(stream, d_hist.p, n_bins);
+        if (!rc) memcpy(hist, h_stage.p, n_bins * sizeof(uint64_t));
+        return rc;
     }
 };
 

@@ -225,58 +225,32 @@ bool overlaps(const void *p, uint64_t p_bytes, const void *q, uint64_t q_bytes)
 
 struct ntk_kmer_sets : Consumer {
     uint32_t kw = 1;
-    uint64_t tiles_cap = 0;                // the three tile arrays hold tiles_cap + 1 words each
-    uint64_t *d_splits = nullptr, *d_tile_counts = nullptr, *d_bases = nullptr;
-    void *d_scan_tmp = nullptr;
-    size_t scan_tmp_bytes = 0;
-    uint64_t *d_bins = nullptr, *h_stage = nullptr;   // kSumWords + kBinsBig words each; h_stage is pinned
+    DeviceArray<uint64_t> d_splits, d_tile_counts, d_bases;   // one word more than the tiles they hold, each
+    DeviceArray<char> d_scan_tmp;          // rocPRIM's temporary storage of the scan over the tile counts
+    DeviceArray<uint64_t> d_bins;          // kSumWords + kBinsBig words
+    Pinned<uint64_t> h_stage;              // likewise
     uint64_t n_launches = 0, n_calls = 0;
 
-    void release_scratch()
-    {
-        for (void *p : {(void *)d_splits, (void *)d_tile_counts, (void *)d_bases, d_scan_tmp})
-            if (p) (void)hipFree(p);
-        d_splits = d_tile_counts = d_bases = nullptr; d_scan_tmp = nullptr;
-        tiles_cap = 0; scan_tmp_bytes = 0;
-    }
+    void release_scratch() { d_splits.release(); d_tile_counts.release(); d_bases.release(); d_scan_tmp.release(); }
 };
 
 namespace {
 
+// the exclusive scan of the tile counts into the bases; item n_tiles is the total
 hipError_t scan_tiles(ntk_kmer_sets *h, void *tmp, size_t &tmp_bytes, uint64_t n_tiles)
 {
-    return rocprim::exclusive_scan(tmp, tmp_bytes, h->d_tile_counts, h->d_bases, (uint64_t)0, (size_t)(n_tiles + 1), rocprim::plus<uint64_t>(),
-                                   h->stream);
+    return rocprim::exclusive_scan(tmp, tmp_bytes, h->d_tile_counts.p, h->d_bases.p, (uint64_t)0, (size_t)(n_tiles + 1),
+                                   rocprim::plus<uint64_t>(), h->stream);
 }
 
-// room for the arrays of n_tiles tiles and the scan over them
+// room for the arrays of n_tiles tiles: a number of tiles that doubles from 1024, and one word more
 int ensure_tiles(ntk_kmer_sets *h, uint64_t n_tiles)
 {
-    if (n_tiles > h->tiles_cap) {
-        CT_HIPCHK(hipStreamSynchronize(h->stream));
-        h->release_scratch();
-        uint64_t want = 1024;
-        while (want < n_tiles) want *= 2;
-        hipError_t e;
-        if ((e = hipMalloc((void **)&h->d_splits, (want + 1) * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&h->d_tile_counts, (want + 1) * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&h->d_bases, (want + 1) * sizeof(uint64_t))) != hipSuccess) {
-            h->release_scratch();
-            return alloc_status(e);
-        }
-        h->tiles_cap = want;
-    }
-    size_t need = 0;
-    CT_HIPCHK(scan_tiles(h, nullptr, need, n_tiles));
-    if (need > h->scan_tmp_bytes || !h->d_scan_tmp) {
-        CT_HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->d_scan_tmp) (void)hipFree(h->d_scan_tmp);
-        h->d_scan_tmp = nullptr; h->scan_tmp_bytes = 0;
-        const hipError_t e = hipMalloc(&h->d_scan_tmp, need ? need : 1);
-        if (e != hipSuccess) return alloc_status(e);
-        h->scan_tmp_bytes = need ? need : 1;
-    }
-    return NTK_OK;
+    const uint64_t words = grow_doubling(0, n_tiles) + 1;
+    int rc = h->d_splits.ensure(h->stream, words, grow_exact);
+    if (!rc) rc = h->d_tile_counts.ensure(h->stream, words, grow_exact);
+    if (!rc) rc = h->d_bases.ensure(h->stream, words, grow_exact);
+    return rc;
 }
 
 int check_list(const uint64_t *keys, const uint64_t *counts, uint64_t n)
@@ -297,16 +271,16 @@ int prepare(ntk_kmer_sets *h, JoinArgs &g, unsigned *blocks)
     if (floor_blocks > 0x7FFFFFFFull) return NTK_ERR_UNSUPPORTED;
     const int rc = ensure_tiles(h, g.n_tiles);
     if (rc) return rc;
-    g.splits = h->d_splits; g.tile_counts = h->d_tile_counts; g.bases = h->d_bases;
+    g.splits = h->d_splits.p; g.tile_counts = h->d_tile_counts.p; g.bases = h->d_bases.p;
     const unsigned fill = grid_for(g.n_tiles, kMinTilesPerBlock, (unsigned)h->n_cu * kBlocksPerCu);
     *blocks = fill < floor_blocks ? (unsigned)floor_blocks : fill;
     const unsigned split_blocks = grid_for(g.n_tiles + 1, kThreads, 0x7FFFFFFFu);
     if (h->kw == 1)
         hipLaunchKernelGGL(ks_split_kernel<1>, dim3(split_blocks), dim3(kThreads), 0, h->stream, g.a_keys, g.n_a, g.b_keys, g.n_b, g.n_tiles,
-                           h->d_splits);
+                           h->d_splits.p);
     else
         hipLaunchKernelGGL(ks_split_kernel<2>, dim3(split_blocks), dim3(kThreads), 0, h->stream, g.a_keys, g.n_a, g.b_keys, g.n_b, g.n_tiles,
-                           h->d_splits);
+                           h->d_splits.p);
     CT_HIPCHK(hipGetLastError());
     h->n_launches++;
     return NTK_OK;
@@ -333,17 +307,12 @@ int ntk_kmer_sets_create(ntk_ctx *ctx, uint32_t key_words, ntk_kmer_sets **out)
     if (key_words != 1 && key_words != 2) return NTK_ERR_BAD_ARG;
     ntk_kmer_sets *h = new (std::nothrow) ntk_kmer_sets();
     if (!h) return NTK_ERR_NOMEM;
-    const int rc = h->bind(ctx, 0, 0);
+    int rc = h->bind(ctx, 0, 0);
     if (rc) { delete h; return rc; }
     h->kw = key_words;
-    const size_t bytes = (kSumWords + kBinsBig) * sizeof(uint64_t);
-    hipError_t e = hipMalloc((void **)&h->d_bins, bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_stage, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        const int st = alloc_status(e);
-        if (h->d_bins) (void)hipFree(h->d_bins);
-        delete h;
-        return st;
+    if ((rc = h->d_bins.ensure(h->stream, kSumWords + kBinsBig, grow_exact)) || (rc = h->h_stage.alloc(kSumWords + kBinsBig))) {
+        ntk_kmer_sets_destroy(h);
+        return rc;
     }
     *out = h;
     return NTK_OK;
@@ -355,8 +324,8 @@ void ntk_kmer_sets_destroy(ntk_kmer_sets *h)
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     h->release_scratch();
-    if (h->d_bins) (void)hipFree(h->d_bins);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
+    h->d_bins.release();
+    h->h_stage.release();
     (void)hipGetLastError();
     delete h;
 }
@@ -374,8 +343,7 @@ int ntk_kmer_sets_stats(ntk_kmer_sets *h, struct ntk_kmer_sets_stats *out)
 {
     if (!h || !out) return NTK_ERR_BAD_ARG;
     out->key_words = h->kw;
-    out->device_bytes = (kSumWords + kBinsBig) * sizeof(uint64_t) + (h->tiles_cap ? 3 * (h->tiles_cap + 1) * sizeof(uint64_t) : 0) +
-                        h->scan_tmp_bytes;
+    out->device_bytes = h->d_bins.bytes() + h->d_splits.bytes() + h->d_tile_counts.bytes() + h->d_bases.bytes() + h->d_scan_tmp.bytes();
     out->n_launches = h->n_launches;
     out->n_calls = h->n_calls;
     return NTK_OK;
@@ -387,16 +355,15 @@ int ntk_kmer_sets_validate_device(ntk_kmer_sets *h, const uint64_t *d_keys, uint
     *n_violations = 0;
     if (n < 2) return NTK_OK;
     CT_HIPCHK(hipSetDevice(h->device));
-    CT_HIPCHK(hipMemsetAsync(h->d_bins, 0, sizeof(uint64_t), h->stream));
+    CT_HIPCHK(hipMemsetAsync(h->d_bins.p, 0, sizeof(uint64_t), h->stream));
     const unsigned blocks = grid_for(n - 1, kThreads, (unsigned)h->n_cu * 8);
-    if (h->kw == 1) hipLaunchKernelGGL(ks_validate_kernel<1>, dim3(blocks), dim3(kThreads), 0, h->stream, d_keys, n, h->d_bins);
-    else hipLaunchKernelGGL(ks_validate_kernel<2>, dim3(blocks), dim3(kThreads), 0, h->stream, d_keys, n, h->d_bins);
+    if (h->kw == 1) hipLaunchKernelGGL(ks_validate_kernel<1>, dim3(blocks), dim3(kThreads), 0, h->stream, d_keys, n, h->d_bins.p);
+    else hipLaunchKernelGGL(ks_validate_kernel<2>, dim3(blocks), dim3(kThreads), 0, h->stream, d_keys, n, h->d_bins.p);
     CT_HIPCHK(hipGetLastError());
     h->n_launches++; h->n_calls++;
-    CT_HIPCHK(hipMemcpyAsync(h->h_stage, h->d_bins, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    CT_HIPCHK(hipStreamSynchronize(h->stream));
-    *n_violations = h->h_stage[0];
-    return NTK_OK;
+    const int rc = h->h_stage.read(h->stream, h->d_bins.p, 1);
+    if (!rc) *n_violations = h->h_stage.p[0];
+    return rc;
 }
 
 int ntk_kmer_sets_compare_device(ntk_kmer_sets *h, const uint64_t *d_a_keys, const uint64_t *d_a_counts, uint64_t n_a,
@@ -408,26 +375,25 @@ int ntk_kmer_sets_compare_device(ntk_kmer_sets *h, const uint64_t *d_a_keys, con
     if (!rc) rc = check_list(d_b_keys, d_b_counts, n_b);
     if (rc) return rc;
     const uint32_t n_bins = n_bins_a * n_bins_b;
-    uint64_t *sums = h->h_stage;
+    uint64_t *sums = h->h_stage.p;
     if (n_a + n_b == 0) {
-        memset(h->h_stage, 0, (kSumWords + n_bins) * sizeof(uint64_t));
+        memset(h->h_stage.p, 0, (kSumWords + n_bins) * sizeof(uint64_t));
     } else {
         JoinArgs g = {};
         g.a_keys = d_a_keys; g.a_counts = d_a_counts; g.n_a = n_a;
         g.b_keys = d_b_keys; g.b_counts = d_b_counts; g.n_b = n_b;
         g.n_bins_a = n_bins_a; g.n_bins_b = n_bins_b;
-        g.sums = h->d_bins; g.hist = h->d_bins + kSumWords;
+        g.sums = h->d_bins.p; g.hist = h->d_bins.p + kSumWords;
         unsigned blocks = 0;
         if ((rc = prepare(h, g, &blocks))) return rc;
-        CT_HIPCHK(hipMemsetAsync(h->d_bins, 0, (kSumWords + n_bins) * sizeof(uint64_t), h->stream));
+        CT_HIPCHK(hipMemsetAsync(h->d_bins.p, 0, (kSumWords + n_bins) * sizeof(uint64_t), h->stream));
         rc = n_bins <= kBinsSmall ? launch_join<kCompare, kBinsSmall>(h, g, blocks) : launch_join<kCompare, kBinsBig>(h, g, blocks);
         if (rc) return rc;
         h->n_calls++;
-        CT_HIPCHK(hipMemcpyAsync(h->h_stage, h->d_bins, (kSumWords + n_bins) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        CT_HIPCHK(hipStreamSynchronize(h->stream));
+        if ((rc = h->h_stage.read(h->stream, h->d_bins.p, kSumWords + n_bins))) return rc;
     }
     if (totals) ks_totals(sums, n_a, n_b, &totals->n_a);
-    if (hist) memcpy(hist, h->h_stage + kSumWords, n_bins * sizeof(uint64_t));
+    if (hist) memcpy(hist, h->h_stage.p + kSumWords, n_bins * sizeof(uint64_t));
     return NTK_OK;
 }
 
@@ -459,12 +425,11 @@ int ntk_kmer_sets_apply_device(ntk_kmer_sets *h, uint32_t op, uint32_t rule, con
     if ((rc = prepare(h, g, &blocks))) return rc;
     h->n_calls++;
     if ((rc = launch_join<kCount, 1>(h, g, blocks))) return rc;
-    CT_HIPCHK(hipMemsetAsync(h->d_tile_counts + g.n_tiles, 0, sizeof(uint64_t), h->stream));   // the scan's last output is the total
-    size_t tmp_bytes = h->scan_tmp_bytes;
-    CT_HIPCHK(scan_tiles(h, h->d_scan_tmp, tmp_bytes, g.n_tiles));
-    CT_HIPCHK(hipMemcpyAsync(h->h_stage, h->d_bases + g.n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    CT_HIPCHK(hipStreamSynchronize(h->stream));
-    const uint64_t total = h->h_stage[0];
+    CT_HIPCHK(hipMemsetAsync(h->d_tile_counts.p + g.n_tiles, 0, sizeof(uint64_t), h->stream));   // the scan's last output is the total
+    rc = with_tmp(h->d_scan_tmp, h->stream, grow_exact,
+                  [&](void *tmp, size_t &tmp_bytes) { return scan_tiles(h, tmp, tmp_bytes, g.n_tiles); });
+    if (rc || (rc = h->h_stage.read(h->stream, h->d_bases.p + g.n_tiles, 1))) return rc;
+    const uint64_t total = h->h_stage.p[0];
     *n = total;
     if (total > cap) return NTK_ERR_CAPACITY;
     if (total == 0) return NTK_OK;

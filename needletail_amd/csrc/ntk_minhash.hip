@@ -201,30 +201,15 @@ __global__ __launch_bounds__(kFilterThreads) void mh_wide_filter_kernel(WideFilt
 }
 
 // hashes and counts on the device, grown on demand (contents are not kept)
-struct Pairs {
-    uint64_t *k = nullptr, *c = nullptr;
-    uint64_t cap = 0;
+struct HashCounts {
+    DeviceArray<uint64_t> k, c;
 
-    void release()
-    {
-        if (k) (void)hipFree(k);
-        if (c) (void)hipFree(c);
-        k = c = nullptr; cap = 0;
-    }
+    void release() { k.release(); c.release(); }
 
-    int ensure(uint64_t n)
+    int ensure(hipStream_t stream, uint64_t n)
     {
-        if (n <= cap) return NTK_OK;
-        release();
-        const uint64_t want = n + n / 2 + 64;
-        hipError_t e;
-        if ((e = hipMalloc((void **)&k, want * sizeof(uint64_t))) != hipSuccess ||
-            (e = hipMalloc((void **)&c, want * sizeof(uint64_t))) != hipSuccess) {
-            release();
-            return alloc_status(e);
-        }
-        cap = want;
-        return NTK_OK;
+        const int rc = k.ensure(stream, n, grow_half_again);
+        return rc ? rc : c.ensure(stream, n, grow_half_again);
     }
 };
 
@@ -233,13 +218,12 @@ struct Pairs {
 struct ntk_minhash : Consumer {
     uint64_t num = 0, scaled = 0, max_hash = kAll;
     uint64_t cap = 0;                 // buffer_entries
-    uint64_t *d_buf = nullptr;        // the candidate buffer
-    uint64_t *d_sorted = nullptr;     // its sorted copy
-    uint64_t *d_ctr = nullptr;        // the three counters, then one word for the lengths rocPRIM reports
-    uint64_t *h_stage = nullptr;      // pinned: 4 words
-    void *d_tmp = nullptr;            // rocPRIM's temporary storage
-    size_t tmp_bytes = 0;
-    Pairs kept, runs, merged, next;   // S; the buffer's runs (or a foreign sketch); S and the runs merged; the next S
+    DeviceArray<uint64_t> d_buf;      // the candidate buffer
+    DeviceArray<uint64_t> d_sorted;   // its sorted copy
+    DeviceArray<uint64_t> d_ctr;      // the three counters, then one word for the lengths rocPRIM reports
+    Pinned<uint64_t> h_stage;         // 4 words: the counters' three, then the word of a length or a threshold
+    DeviceArray<char> d_tmp;          // rocPRIM's temporary storage
+    HashCounts kept, runs, merged, next;   // S; the buffer's runs (or a foreign sketch); S and the runs merged; the next S
     uint64_t n_kept = 0, tau = kAll;
     uint64_t fill = 0;                // buffer slots in use (the device counter's value between launches)
     uint64_t holes = 0;               // of which padding (likewise)
@@ -252,39 +236,6 @@ struct ntk_minhash : Consumer {
 
 namespace {
 
-int ensure_tmp(ntk_minhash *m, size_t bytes)
-{
-    if (bytes <= m->tmp_bytes) return NTK_OK;
-    CT_HIPCHK(hipStreamSynchronize(m->stream));
-    if (m->d_tmp) (void)hipFree(m->d_tmp);
-    m->d_tmp = nullptr; m->tmp_bytes = 0;
-    const hipError_t e = hipMalloc(&m->d_tmp, bytes);
-    if (e != hipSuccess) return alloc_status(e);
-    m->tmp_bytes = bytes;
-    return NTK_OK;
-}
-
-// run(tmp, bytes): a rocPRIM call; first its size query, then the call on the handle's temporary storage
-template <class Run>
-int with_tmp(ntk_minhash *m, Run run)
-{
-    size_t bytes = 0;
-    CT_HIPCHK(run(nullptr, bytes));
-    const int rc = ensure_tmp(m, bytes ? bytes : 1);
-    if (rc) return rc;
-    CT_HIPCHK(run(m->d_tmp, bytes));
-    return NTK_OK;
-}
-
-// a device word on the host (synchronises)
-int read_word(ntk_minhash *m, const uint64_t *d, uint64_t *out)
-{
-    CT_HIPCHK(hipMemcpyAsync(m->h_stage + 3, d, sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
-    CT_HIPCHK(hipStreamSynchronize(m->stream));
-    *out = m->h_stage[3];
-    return NTK_OK;
-}
-
 // the device counters on the host (synchronises)
 struct Counters {
     uint64_t fill, windows, holes;
@@ -292,9 +243,9 @@ struct Counters {
 
 int read_counters(ntk_minhash *m, Counters *c)
 {
-    CT_HIPCHK(hipMemcpyAsync(m->h_stage, m->d_ctr, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
-    CT_HIPCHK(hipStreamSynchronize(m->stream));
-    c->fill = m->h_stage[kCtrFill]; c->windows = m->h_stage[kCtrWindows]; c->holes = m->h_stage[kCtrHoles];
+    const int rc = m->h_stage.read(m->stream, m->d_ctr.p, 3);
+    if (rc) return rc;
+    c->fill = m->h_stage.p[kCtrFill]; c->windows = m->h_stage.p[kCtrWindows]; c->holes = m->h_stage.p[kCtrHoles];
     return NTK_OK;
 }
 
@@ -312,48 +263,46 @@ void take_counters(ntk_minhash *m, const Counters &c)
 // marked (ntk_minhash::failed) and refuses everything but reset, which zeroes both.
 int write_counters(ntk_minhash *m)
 {
-    m->h_stage[kCtrFill] = m->fill; m->h_stage[kCtrWindows] = m->windows; m->h_stage[kCtrHoles] = m->holes;
-    CT_HIPCHK(hipMemcpyAsync(m->d_ctr, m->h_stage, 3 * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
-    CT_HIPCHK(hipStreamSynchronize(m->stream));
-    return NTK_OK;
+    m->h_stage.p[kCtrFill] = m->fill; m->h_stage.p[kCtrWindows] = m->windows; m->h_stage.p[kCtrHoles] = m->holes;
+    return m->h_stage.write(m->stream, m->d_ctr.p, 3);
 }
 
 // S := S combined with the n sorted unique pairs of m->runs (counts of equal hashes add), cut by the handle's rule; tau follows
 int combine(ntk_minhash *m, uint64_t n)
 {
     if (n == 0) return NTK_OK;
-    uint64_t *d_len = m->d_ctr + 3;
-    Pairs *result = &m->runs;
+    uint64_t *d_len = m->d_ctr.p + 3;
+    HashCounts *result = &m->runs;
     uint64_t n_result = n;
     if (m->n_kept) {
         const uint64_t total = m->n_kept + n;
-        int rc = m->merged.ensure(total);
-        if (!rc) rc = m->next.ensure(total);
+        int rc = m->merged.ensure(m->stream, total);
+        if (!rc) rc = m->next.ensure(m->stream, total);
         if (rc) return rc;
-        rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
-            return rocprim::merge(tmp, bytes, m->kept.k, m->runs.k, m->merged.k, m->kept.c, m->runs.c, m->merged.c, (size_t)m->n_kept,
-                                  (size_t)n, rocprim::less<uint64_t>(), m->stream);
+        rc = with_tmp(m->d_tmp, m->stream, grow_exact, [&](void *tmp, size_t &bytes) {
+            return rocprim::merge(tmp, bytes, m->kept.k.p, m->runs.k.p, m->merged.k.p, m->kept.c.p, m->runs.c.p, m->merged.c.p,
+                                  (size_t)m->n_kept, (size_t)n, rocprim::less<uint64_t>(), m->stream);
         });
         if (rc) return rc;
-        rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
-            return rocprim::reduce_by_key(tmp, bytes, m->merged.k, m->merged.c, (size_t)total, m->next.k, m->next.c, d_len,
+        rc = with_tmp(m->d_tmp, m->stream, grow_exact, [&](void *tmp, size_t &bytes) {
+            return rocprim::reduce_by_key(tmp, bytes, m->merged.k.p, m->merged.c.p, (size_t)total, m->next.k.p, m->next.c.p, d_len,
                                           rocprim::plus<uint64_t>(), rocprim::equal_to<uint64_t>(), m->stream);
         });
         if (rc) return rc;
-        if ((rc = read_word(m, d_len, &n_result))) return rc;
+        if ((rc = m->h_stage.read(m->stream, d_len, 1, 3))) return rc;
+        n_result = m->h_stage.p[3];
         result = &m->next;
     }
     // the cut: the num smallest; with `scaled` nothing above max_hash ever got here
     if (m->num && n_result > m->num) n_result = m->num;
-    Pairs old = m->kept;
+    const HashCounts old = m->kept;
     m->kept = *result;
     *result = old;
     m->n_kept = n_result;
     if (m->num && n_result == m->num) {
-        uint64_t last = 0;
-        const int rc = read_word(m, m->kept.k + (n_result - 1), &last);
+        const int rc = m->h_stage.read(m->stream, m->kept.k.p + (n_result - 1), 1, 3);
         if (rc) return rc;
-        m->tau = last;   // only ever falls: the num-th smallest of a growing multiset
+        m->tau = m->h_stage.p[3];   // only ever falls: the num-th smallest of a growing multiset
     }
     m->n_merges++;
     return NTK_OK;
@@ -367,19 +316,18 @@ int flush(ntk_minhash *m)
     CT_HIPCHK(hipSetDevice(m->device));
     if (m->fill > m->holes) {
         const uint64_t n = m->fill - m->holes;
-        int rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
-            return rocprim::radix_sort_keys(tmp, bytes, m->d_buf, m->d_sorted, (size_t)m->fill, 0u, 64u, m->stream);
+        int rc = with_tmp(m->d_tmp, m->stream, grow_exact, [&](void *tmp, size_t &bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, m->d_buf.p, m->d_sorted.p, (size_t)m->fill, 0u, 64u, m->stream);
         });
         if (rc) return rc;
-        if ((rc = m->runs.ensure(n))) return rc;
-        uint64_t *d_len = m->d_ctr + 3;
-        rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
-            return rocprim::run_length_encode(tmp, bytes, m->d_sorted, (unsigned int)n, m->runs.k, m->runs.c, d_len, m->stream);
+        if ((rc = m->runs.ensure(m->stream, n))) return rc;
+        uint64_t *d_len = m->d_ctr.p + 3;
+        rc = with_tmp(m->d_tmp, m->stream, grow_exact, [&](void *tmp, size_t &bytes) {
+            return rocprim::run_length_encode(tmp, bytes, m->d_sorted.p, (unsigned int)n, m->runs.k.p, m->runs.c.p, d_len, m->stream);
         });
         if (rc) return rc;
-        uint64_t n_runs = 0;
-        if ((rc = read_word(m, d_len, &n_runs))) return rc;
-        if ((rc = combine(m, n_runs))) return rc;
+        if ((rc = m->h_stage.read(m->stream, d_len, 1, 3))) return rc;
+        if ((rc = combine(m, m->h_stage.p[3]))) return rc;
     }
     m->fill = m->holes = 0;
     return write_counters(m);
@@ -461,7 +409,7 @@ int settled(ntk_minhash *m, int rc)
 Candidates candidates(const ntk_minhash *m, uint32_t slabs)
 {
     Candidates c;
-    c.buf = m->d_buf; c.cap = m->cap; c.ctr = m->d_ctr; c.tau = m->tau; c.slabs = slabs;
+    c.buf = m->d_buf.p; c.cap = m->cap; c.ctr = m->d_ctr.p; c.tau = m->tau; c.slabs = slabs;
     return c;
 }
 
@@ -485,12 +433,11 @@ int ntk_minhash_create(ntk_ctx *ctx, uint32_t k, uint32_t path, uint64_t num, ui
     if (rc) { delete m; return rc; }
     m->num = num; m->scaled = scaled; m->max_hash = scaled ? kAll / scaled : kAll;
     m->cap = buffer_entries;
-    hipError_t e = hipMalloc((void **)&m->d_buf, m->cap * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_sorted, m->cap * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_ctr, 4 * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&m->h_stage, 4 * sizeof(uint64_t), hipHostMallocDefault);
-    rc = e == hipSuccess ? ntk_minhash_reset(m) : alloc_status(e);
-    if (rc) { ntk_minhash_destroy(m); return rc; }
+    if ((rc = m->d_buf.ensure(m->stream, m->cap, grow_exact)) || (rc = m->d_sorted.ensure(m->stream, m->cap, grow_exact)) ||
+        (rc = m->d_ctr.ensure(m->stream, 4, grow_exact)) || (rc = m->h_stage.alloc(4)) || (rc = ntk_minhash_reset(m))) {
+        ntk_minhash_destroy(m);
+        return rc;
+    }
     *out = m;
     return NTK_OK;
 }
@@ -501,10 +448,9 @@ void ntk_minhash_destroy(ntk_minhash *m)
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
     m->scratch.release();
-    for (Pairs *p : {&m->kept, &m->runs, &m->merged, &m->next}) p->release();
-    for (void *p : {(void *)m->d_buf, (void *)m->d_sorted, (void *)m->d_ctr, m->d_tmp})
-        if (p) (void)hipFree(p);
-    if (m->h_stage) (void)hipHostFree(m->h_stage);
+    for (HashCounts *p : {&m->kept, &m->runs, &m->merged, &m->next}) p->release();
+    m->d_buf.release(); m->d_sorted.release(); m->d_ctr.release(); m->d_tmp.release();
+    m->h_stage.release();
     (void)hipGetLastError();
     delete m;
 }
@@ -513,7 +459,7 @@ int ntk_minhash_reset(ntk_minhash *m)
 {
     if (!m) return NTK_ERR_BAD_ARG;
     CT_HIPCHK(hipSetDevice(m->device));
-    CT_HIPCHK(hipMemsetAsync(m->d_ctr, 0, 4 * sizeof(uint64_t), m->stream));
+    CT_HIPCHK(hipMemsetAsync(m->d_ctr.p, 0, 4 * sizeof(uint64_t), m->stream));
     m->n_kept = 0; m->fill = 0; m->holes = 0; m->windows = 0; m->ends_seen = 0; m->n_merges = 0; m->n_redone = 0;
     m->tau = m->max_hash;   // ~0 with `num`
     m->failed = 0;
@@ -532,9 +478,7 @@ int ntk_minhash_add_device(ntk_minhash *m, const uint8_t *d_seq, const uint8_t *
     if (m->k > 32) {
         WideFilterArgs a;
         a.seq = d_seq; a.n_bytes = n_bytes; a.k = m->k;
-        a.cutoff = (p->flags >> 8) & 0xFF;
-        a.qual = a.cutoff ? d_qual : nullptr;
-        if (!a.qual) a.cutoff = 0;
+        set_quality(a, p, d_qual);
         const uint64_t runs = (n_bytes + kLaneRun - 1) / kLaneRun;
         return run_range(m, 0, runs, kLaneRun, [&](uint64_t lo, uint64_t hi, uint32_t slabs) {
             a.run_lo = lo; a.run_hi = hi; a.c = candidates(m, slabs);
@@ -544,7 +488,7 @@ int ntk_minhash_add_device(ntk_minhash *m, const uint8_t *d_seq, const uint8_t *
     // of every chunk only the windows ending at or after its start are taken
     return for_each_chunk(*m, m->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         FilterArgs a;
-        a.values = m->scratch.d_values; a.valid16 = m->scratch.d_valid16;
+        a.values = m->scratch.d_values.p; a.valid16 = m->scratch.d_valid16.p;
         return run_range(m, c.skip(), c.len(), 1, [&](uint64_t lo, uint64_t hi, uint32_t slabs) {
             a.first = lo; a.n = hi; a.c = candidates(m, slabs);
             const uint64_t rounds = (hi - lo + kPerLane - 1) / kPerLane;
@@ -579,8 +523,8 @@ int ntk_minhash_read(ntk_minhash *m, uint64_t *hashes, uint64_t *counts, uint64_
     *n = m->n_kept;
     if (m->n_kept > cap) return NTK_ERR_CAPACITY;
     if (m->n_kept == 0) return NTK_OK;
-    CT_HIPCHK(hipMemcpyAsync(hashes, m->kept.k, m->n_kept * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
-    CT_HIPCHK(hipMemcpyAsync(counts, m->kept.c, m->n_kept * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
+    CT_HIPCHK(hipMemcpyAsync(hashes, m->kept.k.p, m->n_kept * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
+    CT_HIPCHK(hipMemcpyAsync(counts, m->kept.c.p, m->n_kept * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
     CT_HIPCHK(hipStreamSynchronize(m->stream));
     return NTK_OK;
 }
@@ -598,14 +542,14 @@ int ntk_minhash_merge(ntk_minhash *m, const uint64_t *hashes, const uint64_t *co
     uint64_t take = 0;
     while (take < n && hashes[take] <= m->tau && (!m->num || take < m->num)) take++;
     if (take) {
-        if ((rc = m->runs.ensure(take))) return rc;
-        CT_HIPCHK(hipMemcpyAsync(m->runs.k, hashes, take * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+        if ((rc = m->runs.ensure(m->stream, take))) return rc;
+        CT_HIPCHK(hipMemcpyAsync(m->runs.k.p, hashes, take * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
         std::vector<uint64_t> ones;
         if (!counts) {
             ones.assign(take, 1);
             counts = ones.data();
         }
-        CT_HIPCHK(hipMemcpyAsync(m->runs.c, counts, take * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+        CT_HIPCHK(hipMemcpyAsync(m->runs.c.p, counts, take * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
         CT_HIPCHK(hipStreamSynchronize(m->stream));   // the caller's arrays are free again
         if ((rc = combine(m, take))) return rc;
     }

@@ -137,41 +137,6 @@ __global__ __launch_bounds__(kPairThreads) void ms_pair_kernel(PairArgs g)
     else pair_wave(g, pair - g.p0, a, ca, na, b, cb, nb);
 }
 
-// a device array that grows by doubling and keeps its contents
-template <class T>
-struct Grown {
-    T *d = nullptr;
-    uint64_t cap = 0;
-
-    void release()
-    {
-        if (d) (void)hipFree(d);
-        d = nullptr; cap = 0;
-    }
-
-    // room for `need` elements, the first `keep` of them kept (synchronises when it grows)
-    int ensure(hipStream_t stream, uint64_t need, uint64_t keep)
-    {
-        if (need <= cap) return NTK_OK;
-        uint64_t want = cap ? cap : 1024;
-        while (want < need) want *= 2;
-        T *fresh = nullptr;
-        const hipError_t e = hipMalloc((void **)&fresh, want * sizeof(T));
-        if (e != hipSuccess) return alloc_status(e);
-        if (keep) {
-            const hipError_t c = hipMemcpyAsync(fresh, d, keep * sizeof(T), hipMemcpyDeviceToDevice, stream);
-            if (c != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-                (void)hipGetLastError();
-                (void)hipFree(fresh);
-                return NTK_ERR_HIP;
-            }
-        }
-        if (d) (void)hipFree(d);
-        d = fresh; cap = want;
-        return NTK_OK;
-    }
-};
-
 }  // namespace
 
 struct ntk_mhset : Consumer {
@@ -180,9 +145,9 @@ struct ntk_mhset : Consumer {
     std::vector<uint64_t> offsets{0};          // host: every sketch's start, and the end of the last
     std::vector<uint64_t> new_hashes, new_counts;   // host staging: the entries of the sketches not yet uploaded
     uint64_t up_sketches = 0, up_entries = 0;  // what the device holds
-    Grown<uint64_t> d_offsets, d_hashes, d_counts, d_cut;
-    uint8_t *d_res = nullptr, *h_res = nullptr;   // the result scratch and its pinned mirror, res_pairs * kResultBytes each
-    uint64_t res_pairs = 0;
+    DeviceArray<uint64_t> d_offsets, d_hashes, d_counts, d_cut;   // grown by doubling, their contents kept
+    DeviceArray<uint8_t> d_res;                // the result scratch: kResultBytes per pair of a sub-block
+    Pinned<uint8_t> h_res;                     // its mirror
     uint64_t n_launches = 0, n_uploads = 0;
 
     uint64_t n_sketches() const { return offsets.size() - 1; }
@@ -196,22 +161,22 @@ int flush(ntk_mhset *s)
 {
     CT_HIPCHK(hipSetDevice(s->device));
     const uint64_t n_sk = s->n_sketches(), n_en = s->n_entries();
-    if (s->up_sketches == n_sk && s->d_offsets.d) return NTK_OK;
-    int rc = s->d_offsets.ensure(s->stream, n_sk + 1, s->up_sketches ? s->up_sketches + 1 : 0);
-    if (!rc) rc = s->d_cut.ensure(s->stream, n_sk + 1, 0);
-    if (!rc) rc = s->d_hashes.ensure(s->stream, n_en + 1, s->up_entries);
-    if (!rc && s->abundance) rc = s->d_counts.ensure(s->stream, n_en + 1, s->up_entries);
+    if (s->up_sketches == n_sk && s->d_offsets.p) return NTK_OK;
+    int rc = s->d_offsets.ensure(s->stream, n_sk + 1, grow_doubling, s->up_sketches ? s->up_sketches + 1 : 0);
+    if (!rc) rc = s->d_cut.ensure(s->stream, n_sk + 1, grow_doubling);
+    if (!rc) rc = s->d_hashes.ensure(s->stream, n_en + 1, grow_doubling, s->up_entries);
+    if (!rc && s->abundance) rc = s->d_counts.ensure(s->stream, n_en + 1, grow_doubling, s->up_entries);
     if (rc) return rc;
     // offsets[up_sketches] is on the device already, or is the leading 0 of an empty device copy
     const uint64_t from = s->up_sketches ? s->up_sketches + 1 : 0;
-    CT_HIPCHK(hipMemcpyAsync(s->d_offsets.d + from, s->offsets.data() + from, (n_sk + 1 - from) * sizeof(uint64_t), hipMemcpyHostToDevice,
+    CT_HIPCHK(hipMemcpyAsync(s->d_offsets.p + from, s->offsets.data() + from, (n_sk + 1 - from) * sizeof(uint64_t), hipMemcpyHostToDevice,
                              s->stream));
     const uint64_t fresh = n_en - s->up_entries;
     if (fresh) {
-        CT_HIPCHK(hipMemcpyAsync(s->d_hashes.d + s->up_entries, s->new_hashes.data(), fresh * sizeof(uint64_t), hipMemcpyHostToDevice,
+        CT_HIPCHK(hipMemcpyAsync(s->d_hashes.p + s->up_entries, s->new_hashes.data(), fresh * sizeof(uint64_t), hipMemcpyHostToDevice,
                                  s->stream));
         if (s->abundance)
-            CT_HIPCHK(hipMemcpyAsync(s->d_counts.d + s->up_entries, s->new_counts.data(), fresh * sizeof(uint64_t), hipMemcpyHostToDevice,
+            CT_HIPCHK(hipMemcpyAsync(s->d_counts.p + s->up_entries, s->new_counts.data(), fresh * sizeof(uint64_t), hipMemcpyHostToDevice,
                                      s->stream));
     }
     CT_HIPCHK(hipStreamSynchronize(s->stream));   // the staging is free again
@@ -221,28 +186,19 @@ int flush(ntk_mhset *s)
     return NTK_OK;
 }
 
+// room for the results of `pairs` pairs, on the device and in its pinned mirror
 int ensure_results(ntk_mhset *s, uint64_t pairs)
 {
-    if (pairs <= s->res_pairs) return NTK_OK;
-    CT_HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->d_res) (void)hipFree(s->d_res);
-    if (s->h_res) (void)hipHostFree(s->h_res);
-    s->d_res = s->h_res = nullptr; s->res_pairs = 0;
-    hipError_t e = hipMalloc((void **)&s->d_res, pairs * kResultBytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_res, pairs * kResultBytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (s->d_res) (void)hipFree(s->d_res);
-        s->d_res = nullptr;
-        return alloc_status(e);
-    }
-    s->res_pairs = pairs;
-    return NTK_OK;
+    if (pairs * kResultBytes <= s->d_res.cap) return NTK_OK;
+    int rc = s->d_res.ensure(s->stream, pairs * kResultBytes, grow_exact);
+    if (!rc && (rc = s->h_res.alloc(pairs * kResultBytes))) s->d_res.release();   // both or neither
+    return rc;
 }
 
 Side side_of(const ntk_mhset *s, uint64_t first, uint64_t n, uint64_t rel, uint64_t stride)
 {
     Side d;
-    d.offsets = s->d_offsets.d; d.hashes = s->d_hashes.d; d.counts = s->abundance ? s->d_counts.d : nullptr; d.cut = s->d_cut.d;
+    d.offsets = s->d_offsets.p; d.hashes = s->d_hashes.p; d.counts = s->abundance ? s->d_counts.p : nullptr; d.cut = s->d_cut.p;
     d.first = first; d.n = n; d.rel = rel; d.stride = stride;
     return d;
 }
@@ -272,9 +228,9 @@ void ntk_mhset_destroy(ntk_mhset *s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
-    for (Grown<uint64_t> *g : {&s->d_offsets, &s->d_hashes, &s->d_counts, &s->d_cut}) g->release();
-    if (s->d_res) (void)hipFree(s->d_res);
-    if (s->h_res) (void)hipHostFree(s->h_res);
+    for (DeviceArray<uint64_t> *g : {&s->d_offsets, &s->d_hashes, &s->d_counts, &s->d_cut}) g->release();
+    s->d_res.release();
+    s->h_res.release();
     (void)hipGetLastError();
     delete s;
 }
@@ -319,9 +275,9 @@ int ntk_mhset_read(ntk_mhset *s, uint64_t index, uint64_t *hashes, uint64_t *cou
     if (len > cap) return NTK_ERR_CAPACITY;
     const int rc = flush(s);
     if (rc || len == 0) return rc;
-    CT_HIPCHK(hipMemcpyAsync(hashes, s->d_hashes.d + lo, len * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+    CT_HIPCHK(hipMemcpyAsync(hashes, s->d_hashes.p + lo, len * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     if (counts && s->abundance)
-        CT_HIPCHK(hipMemcpyAsync(counts, s->d_counts.d + lo, len * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        CT_HIPCHK(hipMemcpyAsync(counts, s->d_counts.p + lo, len * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     CT_HIPCHK(hipStreamSynchronize(s->stream));
     if (counts && !s->abundance)
         for (uint64_t i = 0; i < len; i++) counts[i] = 1;
@@ -335,7 +291,7 @@ int ntk_mhset_stats(ntk_mhset *s, struct ntk_mhset_stats *out)
     out->n_entries = s->n_entries();
     out->abundance = s->abundance;
     out->block_pairs = s->block_pairs;
-    out->device_bytes = (s->d_offsets.cap + s->d_hashes.cap + s->d_counts.cap + s->d_cut.cap) * sizeof(uint64_t) + s->res_pairs * kResultBytes;
+    out->device_bytes = s->d_offsets.bytes() + s->d_hashes.bytes() + s->d_counts.bytes() + s->d_cut.bytes() + s->d_res.bytes();
     out->n_launches = s->n_launches;
     out->n_uploads = s->n_uploads;
     return NTK_OK;
@@ -360,14 +316,14 @@ int ntk_mhset_compare(ntk_mhset *rows, uint64_t row0, uint64_t n_rows, ntk_mhset
     CutArgs c;
     const ntk_mhset *both[2] = {rows, cols};
     for (int i = 0; i < 2; i++) {
-        c.offsets[i] = both[i]->d_offsets.d; c.hashes[i] = both[i]->d_hashes.d; c.cut[i] = both[i]->d_cut.d;
+        c.offsets[i] = both[i]->d_offsets.p; c.hashes[i] = both[i]->d_hashes.p; c.cut[i] = both[i]->d_cut.p;
     }
     c.first[0] = row0; c.n[0] = n_rows; c.first[1] = col0; c.n[1] = n_cols;
     c.max_hash = max_hash;
     hipLaunchKernelGGL(ms_cut_kernel, dim3(grid_for(n_rows + n_cols, kThreads, 0x7FFFFFFFu)), dim3(kThreads), 0, stream, c);
     CT_HIPCHK(hipGetLastError());
-    if (n_a) CT_HIPCHK(hipMemcpyAsync(n_a, rows->d_cut.d + row0, n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    if (n_b) CT_HIPCHK(hipMemcpyAsync(n_b, cols->d_cut.d + col0, n_cols * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    if (n_a) CT_HIPCHK(hipMemcpyAsync(n_a, rows->d_cut.p + row0, n_rows * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    if (n_b) CT_HIPCHK(hipMemcpyAsync(n_b, cols->d_cut.p + col0, n_cols * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
 
     // what is copied back of a sub-block's results: the arrays lie in this order, and the copy ends with the last one asked for
     const uint64_t fields = norm2_b ? 32 : norm2_a ? 24 : dot ? 16 : (n_shared || n_union) ? 8 : 0;
@@ -385,8 +341,8 @@ int ntk_mhset_compare(ntk_mhset *rows, uint64_t row0, uint64_t n_rows, ntk_mhset
         const Side col_side = side_of(cols, col0 + c_lo, c_n, c_lo, 1);
         PairArgs g;
         g.p0 = p0; g.np = np; g.num = num;
-        g.n_shared = (uint32_t *)s->d_res; g.n_union = g.n_shared + np;
-        g.dot = (double *)(s->d_res + 8 * np);
+        g.n_shared = (uint32_t *)s->d_res.p; g.n_union = g.n_shared + np;
+        g.dot = (double *)(s->d_res.p + 8 * np);
         double *d_norm_a = g.dot + np, *d_norm_b = d_norm_a + np;
         for (int pass = 0; pass < (norm2_b ? 2 : 1); pass++) {
             g.walk = pass ? col_side : row_side; g.search = pass ? row_side : col_side;
@@ -397,13 +353,12 @@ int ntk_mhset_compare(ntk_mhset *rows, uint64_t row0, uint64_t n_rows, ntk_mhset
             CT_HIPCHK(hipGetLastError());
             s->n_launches++;
         }
-        CT_HIPCHK(hipMemcpyAsync(s->h_res, s->d_res, fields * np, hipMemcpyDeviceToHost, stream));
-        CT_HIPCHK(hipStreamSynchronize(stream));
-        if (n_shared) memcpy(n_shared + p0, s->h_res, np * sizeof(uint32_t));
-        if (n_union) memcpy(n_union + p0, s->h_res + 4 * np, np * sizeof(uint32_t));
-        if (dot) memcpy(dot + p0, s->h_res + 8 * np, np * sizeof(double));
-        if (norm2_a) memcpy(norm2_a + p0, s->h_res + 16 * np, np * sizeof(double));
-        if (norm2_b) memcpy(norm2_b + p0, s->h_res + 24 * np, np * sizeof(double));
+        if ((rc = s->h_res.read(stream, s->d_res.p, fields * np))) return rc;
+        if (n_shared) memcpy(n_shared + p0, s->h_res.p, np * sizeof(uint32_t));
+        if (n_union) memcpy(n_union + p0, s->h_res.p + 4 * np, np * sizeof(uint32_t));
+        if (dot) memcpy(dot + p0, s->h_res.p + 8 * np, np * sizeof(double));
+        if (norm2_a) memcpy(norm2_a + p0, s->h_res.p + 16 * np, np * sizeof(double));
+        if (norm2_b) memcpy(norm2_b + p0, s->h_res.p + 24 * np, np * sizeof(double));
     }
     return NTK_OK;
 }

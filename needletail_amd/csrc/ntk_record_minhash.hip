@@ -373,61 +373,25 @@ __global__ void rmh_accept_kernel(AcceptArgs a)
     (void)__hip_atomic_fetch_min(a.ctr + kCtrMinRec, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// a device array grown on demand; `total` is the handle's sum of device bytes
-template <class T>
-struct Dev {
-    T *p = nullptr;
-    uint64_t cap = 0;
-
-    void release(uint64_t &total)
-    {
-        if (p) (void)hipFree(p);
-        total -= cap * sizeof(T);
-        p = nullptr; cap = 0;
-    }
-
-    // room for n entries; the first `keep` stay (the stream is synchronised when it grows)
-    int ensure(uint64_t n, uint64_t &total, hipStream_t stream, uint64_t keep = 0, bool exact = false)
-    {
-        if (n <= cap) return NTK_OK;
-        CT_HIPCHK(hipStreamSynchronize(stream));   // queued kernels may still use the old array
-        const uint64_t want = exact ? n : n + n / 2 + 64;
-        T *q = nullptr;
-        const hipError_t e = hipMalloc((void **)&q, want * sizeof(T));
-        if (e != hipSuccess) return alloc_status(e);
-        if (keep) {
-            if (hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) {
-                (void)hipFree(q);
-                (void)hipGetLastError();
-                return NTK_ERR_HIP;
-            }
-        }
-        release(total);
-        p = q; cap = want;
-        total += want * sizeof(T);
-        return NTK_OK;
-    }
-};
-
 }  // namespace
 
 struct ntk_record_minhash : Consumer {
     uint64_t num = 0, scaled = 0, max_hash = kAll, limit = kAll;
     uint64_t cap = 0;                           // buffer_entries
-    uint64_t *h_stage = nullptr;                // pinned: kCtrWords words
-    uint64_t bytes = 0;                         // device bytes of the arrays below (the scratch is counted on top)
+    Pinned<uint64_t> h_stage;                   // kCtrWords words
     MaterialiseScratch scratch;
-    Dev<uint64_t> ctr;                          // kCtrFill: slots reserved; kCtrList, kCtrMinRec: rmh_accept_kernel's
-    Dev<uint64_t> b_hash; Dev<uint32_t> b_rec;  // the candidate buffer
-    Dev<uint64_t> lo, tau, windows, start, seg_start, len;   // per record (start, len: one more)
-    Dev<uint32_t> list_a, list_b;               // the round's records and the next round's
-    Dev<uint32_t> k_rec; Dev<uint64_t> k_hash, k_cnt;        // K
+    DeviceArray<uint64_t> ctr;                  // kCtrFill: slots reserved; kCtrList, kCtrMinRec: rmh_accept_kernel's
+    DeviceArray<uint64_t> b_hash;               // the candidate buffer
+    DeviceArray<uint32_t> b_rec;
+    DeviceArray<uint64_t> lo, tau, windows, start, seg_start, len;   // per record (start, len: one more)
+    DeviceArray<uint32_t> list_a, list_b;       // the round's records and the next round's
+    DeviceArray<uint32_t> k_rec;                // K
+    DeviceArray<uint64_t> k_hash, k_cnt;
     // a fold's work arrays: its entries (the kept ones first), two index arrays, sorted keys, the order's records, hashes, counts and
     // heads with their scans, and the groups
-    Dev<uint64_t> w_hash, s_hash, o_cnt, o_sum, g_hash, g_begin, g_end;
-    Dev<uint32_t> w_rec, idx_a, idx_b, r_a, r_b, o_head, o_group, g_rec;
-    Dev<char> tmp;                              // rocPRIM's temporary storage
+    DeviceArray<uint64_t> w_hash, s_hash, o_cnt, o_sum, g_hash, g_begin, g_end;
+    DeviceArray<uint32_t> w_rec, idx_a, idx_b, r_a, r_b, o_head, o_group, g_rec;
+    DeviceArray<char> tmp;                      // rocPRIM's temporary storage
     std::vector<uint64_t> h_offsets;            // the batch's record starts, read back once per run
     uint64_t n_records = 0;                     // of the held result
     bool held = false;                          // a result is held (n_records may be 0)
@@ -436,50 +400,28 @@ struct ntk_record_minhash : Consumer {
     uint64_t n_rounds = 0, n_retried = 0, n_redone = 0, sum_windows = 0;
     int failed = 0;                             // the status of a run that failed halfway
 
+    // f(array) for every device array above (the scratch is apart): what release_all frees is what stats counts
+    template <class F>
+    void each_array(F f)
+    {
+        for (DeviceArray<uint64_t> *d : {&ctr, &b_hash, &lo, &tau, &windows, &start, &seg_start, &len, &k_hash, &k_cnt, &w_hash, &s_hash,
+                                         &o_cnt, &o_sum, &g_hash, &g_begin, &g_end})
+            f(*d);
+        for (DeviceArray<uint32_t> *d : {&b_rec, &list_a, &list_b, &k_rec, &w_rec, &idx_a, &idx_b, &r_a, &r_b, &o_head, &o_group, &g_rec})
+            f(*d);
+        f(tmp);
+    }
+
     void release_all()
     {
         scratch.release();
-        ctr.release(bytes); b_hash.release(bytes); b_rec.release(bytes);
-        for (Dev<uint64_t> *d : {&lo, &tau, &windows, &start, &seg_start, &len, &k_hash, &k_cnt, &w_hash, &s_hash, &o_cnt, &o_sum, &g_hash,
-                                 &g_begin, &g_end})
-            d->release(bytes);
-        for (Dev<uint32_t> *d : {&list_a, &list_b, &k_rec, &w_rec, &idx_a, &idx_b, &r_a, &r_b, &o_head, &o_group, &g_rec}) d->release(bytes);
-        tmp.release(bytes);
+        each_array([](auto &d) { d.release(); });
     }
 };
 
 namespace {
 
 using Handle = ntk_record_minhash;
-
-// run(tmp, bytes): a rocPRIM call; first its size query, then the call on the handle's temporary storage
-template <class Run>
-int with_tmp(Handle *m, Run run)
-{
-    size_t need = 0;
-    CT_HIPCHK(run(nullptr, need));
-    const int rc = m->tmp.ensure(need ? need : 1, m->bytes, m->stream);
-    if (rc) return rc;
-    CT_HIPCHK(run((void *)m->tmp.p, need));
-    return NTK_OK;
-}
-
-// n device words on the host, in h_stage (synchronises)
-int read_words(Handle *m, const uint64_t *d, uint32_t n)
-{
-    CT_HIPCHK(hipMemcpyAsync(m->h_stage, d, n * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
-    CT_HIPCHK(hipStreamSynchronize(m->stream));
-    return NTK_OK;
-}
-
-// a device word := v (synchronises: the stage is free again)
-int write_word(Handle *m, uint64_t *d, uint64_t v)
-{
-    m->h_stage[0] = v;
-    CT_HIPCHK(hipMemcpyAsync(d, m->h_stage, sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
-    CT_HIPCHK(hipStreamSynchronize(m->stream));
-    return NTK_OK;
-}
 
 inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
@@ -493,14 +435,14 @@ int fold(Handle *m, uint64_t n_records)
     if (m->fill == 0) return NTK_OK;
     int rc;
     const uint64_t r0 = m->fold_from < n_records ? m->fold_from : 0;
-    if ((rc = read_words(m, m->start.p + r0, 1))) return rc;
-    const uint64_t p = m->h_stage[0], n_suffix = m->n_kept - p, n = n_suffix + m->fill, n_seg = n_records - r0;
+    if ((rc = m->h_stage.read(m->stream, m->start.p + r0, 1))) return rc;
+    const uint64_t p = m->h_stage.p[0], n_suffix = m->n_kept - p, n = n_suffix + m->fill, n_seg = n_records - r0;
     if (n >> 32) return NTK_ERR_CAPACITY;
     hipStream_t st = m->stream;
-    for (Dev<uint64_t> *d : {&m->w_hash, &m->s_hash, &m->o_cnt, &m->o_sum, &m->g_hash, &m->g_begin, &m->g_end})
-        if ((rc = d->ensure(n, m->bytes, st))) return rc;
-    for (Dev<uint32_t> *d : {&m->w_rec, &m->idx_a, &m->idx_b, &m->r_a, &m->r_b, &m->o_head, &m->o_group, &m->g_rec})
-        if ((rc = d->ensure(n, m->bytes, st))) return rc;
+    for (DeviceArray<uint64_t> *d : {&m->w_hash, &m->s_hash, &m->o_cnt, &m->o_sum, &m->g_hash, &m->g_begin, &m->g_end})
+        if ((rc = d->ensure(st, n, grow_half_again))) return rc;
+    for (DeviceArray<uint32_t> *d : {&m->w_rec, &m->idx_a, &m->idx_b, &m->r_a, &m->r_b, &m->o_head, &m->o_group, &m->g_rec})
+        if ((rc = d->ensure(st, n, grow_half_again))) return rc;
     if (n_suffix) {
         CT_HIPCHK(hipMemcpyAsync(m->w_hash.p, m->k_hash.p + p, n_suffix * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
         CT_HIPCHK(hipMemcpyAsync(m->w_rec.p, m->k_rec.p + p, n_suffix * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
@@ -510,7 +452,7 @@ int fold(Handle *m, uint64_t n_records)
     const unsigned blocks = blocks_for(n);
     hipLaunchKernelGGL(rmh_iota_kernel, dim3(blocks), dim3(kThreads), 0, st, m->idx_a.p, n);
     CT_HIPCHK(hipGetLastError());
-    rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
+    rc = with_tmp(m->tmp, st, grow_half_again, [&](void *tmp, size_t &bytes) {
         return rocprim::radix_sort_pairs(tmp, bytes, m->w_hash.p, m->s_hash.p, m->idx_a.p, m->idx_b.p, (size_t)n, 0u, 64u, st);
     });
     if (rc) return rc;
@@ -518,7 +460,7 @@ int fold(Handle *m, uint64_t n_records)
     CT_HIPCHK(hipGetLastError());
     unsigned rec_bits = 1;
     while (rec_bits < 32 && (n_records - 1) >> rec_bits) rec_bits++;
-    rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
+    rc = with_tmp(m->tmp, st, grow_half_again, [&](void *tmp, size_t &bytes) {
         return rocprim::radix_sort_pairs(tmp, bytes, m->r_a.p, m->r_b.p, m->idx_b.p, m->idx_a.p, (size_t)n, 0u, rec_bits, st);
     });
     if (rc) return rc;
@@ -528,11 +470,11 @@ int fold(Handle *m, uint64_t n_records)
     h.out_hash = m->s_hash.p; h.out_cnt = m->o_cnt.p; h.head = m->o_head.p;   // (the first sort's keys are not needed again)
     hipLaunchKernelGGL(rmh_heads_kernel, dim3(blocks), dim3(kThreads), 0, st, h);
     CT_HIPCHK(hipGetLastError());
-    rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
+    rc = with_tmp(m->tmp, st, grow_half_again, [&](void *tmp, size_t &bytes) {
         return rocprim::inclusive_scan(tmp, bytes, m->o_head.p, m->o_group.p, (size_t)n, rocprim::plus<uint32_t>(), st);
     });
     if (rc) return rc;
-    rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
+    rc = with_tmp(m->tmp, st, grow_half_again, [&](void *tmp, size_t &bytes) {
         return rocprim::inclusive_scan(tmp, bytes, m->o_cnt.p, m->o_sum.p, (size_t)n, rocprim::plus<uint64_t>(), st);
     });
     if (rc) return rc;
@@ -542,21 +484,21 @@ int fold(Handle *m, uint64_t n_records)
     hipLaunchKernelGGL(rmh_groups_kernel, dim3(blocks), dim3(kThreads), 0, st, g);
     CT_HIPCHK(hipGetLastError());
     // the number of groups: the last entry's
-    CT_HIPCHK(hipMemcpyAsync(m->h_stage, m->o_group.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CT_HIPCHK(hipMemcpyAsync(m->h_stage.p, m->o_group.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     CT_HIPCHK(hipStreamSynchronize(st));
-    const uint64_t n_groups = *(const uint32_t *)m->h_stage;
+    const uint64_t n_groups = *(const uint32_t *)m->h_stage.p;
     hipLaunchKernelGGL(rmh_segments_kernel, dim3(blocks_for(n_seg + 1)), dim3(kThreads), 0, st, m->g_rec.p, n_groups, r0, n_seg, m->limit,
                        m->seg_start.p, m->len.p);
     CT_HIPCHK(hipGetLastError());
-    rc = with_tmp(m, [&](void *tmp, size_t &bytes) {
+    rc = with_tmp(m->tmp, st, grow_half_again, [&](void *tmp, size_t &bytes) {
         return rocprim::exclusive_scan(tmp, bytes, m->len.p, m->start.p + r0, p, (size_t)(n_seg + 1), rocprim::plus<uint64_t>(), st);
     });
     if (rc) return rc;
-    if ((rc = read_words(m, m->start.p + n_records, 1))) return rc;
-    const uint64_t n_kept = m->h_stage[0];
+    if ((rc = m->h_stage.read(st, m->start.p + n_records, 1))) return rc;
+    const uint64_t n_kept = m->h_stage.p[0];
     if (n_kept >> 32) return NTK_ERR_CAPACITY;
-    if ((rc = m->k_rec.ensure(n_kept, m->bytes, st, p)) || (rc = m->k_hash.ensure(n_kept, m->bytes, st, p)) ||
-        (rc = m->k_cnt.ensure(n_kept, m->bytes, st, p)))
+    if ((rc = m->k_rec.ensure(st, n_kept, grow_half_again, p)) || (rc = m->k_hash.ensure(st, n_kept, grow_half_again, p)) ||
+        (rc = m->k_cnt.ensure(st, n_kept, grow_half_again, p)))
         return rc;
     KeepArgs k;
     k.g_rec = m->g_rec.p; k.g_hash = m->g_hash.p; k.g_begin = m->g_begin.p; k.g_end = m->g_end.p; k.seg_start = m->seg_start.p;
@@ -566,7 +508,8 @@ int fold(Handle *m, uint64_t n_records)
     CT_HIPCHK(hipGetLastError());
     m->n_kept = n_kept;
     m->fill = 0; m->fold_from = kAll;
-    return write_word(m, m->ctr.p + kCtrFill, 0);
+    m->h_stage.p[0] = 0;
+    return m->h_stage.write(st, m->ctr.p + kCtrFill, 1);
 }
 
 // the record that holds window end e, or the one before it (host offsets; never above the true one)
@@ -593,19 +536,20 @@ int run_range(Handle *m, uint64_t n_records, uint64_t lo, uint64_t hi, uint64_t 
     auto take = [&](uint64_t a, uint64_t b) -> int {
         launch(a, b);
         CT_HIPCHK(hipGetLastError());
-        if ((rc = read_words(m, m->ctr.p + kCtrFill, 1))) return rc;
+        if ((rc = m->h_stage.read(m->stream, m->ctr.p + kCtrFill, 1))) return rc;
         if (from < m->fold_from) m->fold_from = from;
         return NTK_OK;
     };
     if ((rc = take(lo, hi))) return rc;
-    if (m->h_stage[0] <= m->cap) { m->fill = m->h_stage[0]; return NTK_OK; }
+    if (m->h_stage.p[0] <= m->cap) { m->fill = m->h_stage.p[0]; return NTK_OK; }
     // it did not fit: its appends are dropped (m->fill still says what was there before) and the range is redone
     m->n_redone++;
-    if ((rc = write_word(m, m->ctr.p + kCtrFill, m->fill)) || (rc = fold(m, n_records))) return rc;
+    m->h_stage.p[0] = m->fill;
+    if ((rc = m->h_stage.write(m->stream, m->ctr.p + kCtrFill, 1)) || (rc = fold(m, n_records))) return rc;
     for (uint64_t a = lo; a < hi; a += m->cap) {
         if ((rc = take(a, hi - a < m->cap ? hi : a + m->cap))) return rc;
-        if (m->h_stage[0] > m->cap) return NTK_ERR_HIP;   // cannot happen
-        m->fill = m->h_stage[0];
+        if (m->h_stage.p[0] > m->cap) return NTK_ERR_HIP;   // cannot happen
+        m->fill = m->h_stage.p[0];
         if ((rc = fold(m, n_records))) return rc;
     }
     return NTK_OK;
@@ -614,7 +558,7 @@ int run_range(Handle *m, uint64_t n_records, uint64_t lo, uint64_t hi, uint64_t 
 Scan scan_of(Handle *m, const Chunk &c, const uint64_t *d_offsets, uint64_t n_records, uint64_t n_bytes)
 {
     Scan s;
-    s.values = m->scratch.d_values; s.valid16 = m->scratch.d_valid16; s.base = c.base;
+    s.values = m->scratch.d_values.p; s.valid16 = m->scratch.d_valid16.p; s.base = c.base;
     s.offsets = d_offsets; s.n_records = n_records; s.n_bytes = n_bytes; s.k = m->k;
     s.lo = m->lo.p; s.tau = m->tau.p;
     s.b.hash = m->b_hash.p; s.b.rec = m->b_rec.p; s.b.cap = m->cap; s.b.fill = m->ctr.p + kCtrFill;
@@ -634,12 +578,13 @@ int run(Handle *m, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes
         return NTK_ERR_NOMEM;
     }
     CT_HIPCHK(hipMemcpyAsync(m->h_offsets.data(), d_offsets, (n_records + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if ((rc = m->ctr.ensure(kCtrWords, m->bytes, st, 0, true)) || (rc = m->b_hash.ensure(m->cap, m->bytes, st, 0, true)) ||
-        (rc = m->b_rec.ensure(m->cap, m->bytes, st, 0, true)))
+    if ((rc = m->ctr.ensure(st, kCtrWords, grow_exact)) || (rc = m->b_hash.ensure(st, m->cap, grow_exact)) ||
+        (rc = m->b_rec.ensure(st, m->cap, grow_exact)))
         return rc;
-    for (Dev<uint64_t> *d : {&m->lo, &m->tau, &m->windows, &m->start, &m->seg_start, &m->len})
-        if ((rc = d->ensure(n_records + 1, m->bytes, st))) return rc;
-    if (m->num && ((rc = m->list_a.ensure(n_records, m->bytes, st)) || (rc = m->list_b.ensure(n_records, m->bytes, st)))) return rc;
+    for (DeviceArray<uint64_t> *d : {&m->lo, &m->tau, &m->windows, &m->start, &m->seg_start, &m->len})
+        if ((rc = d->ensure(st, n_records + 1, grow_half_again))) return rc;
+    if (m->num && ((rc = m->list_a.ensure(st, n_records, grow_half_again)) || (rc = m->list_b.ensure(st, n_records, grow_half_again))))
+        return rc;
     CT_HIPCHK(hipMemsetAsync(m->ctr.p, 0, kCtrWords * sizeof(uint64_t), st));
     CT_HIPCHK(hipMemsetAsync(m->lo.p, 0, n_records * sizeof(uint64_t), st));
     CT_HIPCHK(hipMemsetAsync(m->windows.p, 0, n_records * sizeof(uint64_t), st));
@@ -669,7 +614,7 @@ int run(Handle *m, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes
     rc = for_each_chunk(*m, m->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         const uint64_t r0 = record_at(m, n_records, n_bytes, c.start), r1 = record_at(m, n_records, n_bytes, c.end - 1) + 1;
         WindowsArgs w;
-        w.valid16 = m->scratch.d_valid16; w.base = c.base; w.lo = c.start; w.hi = c.end;
+        w.valid16 = m->scratch.d_valid16.p; w.base = c.base; w.lo = c.start; w.hi = c.end;
         w.offsets = d_offsets; w.n_bytes = n_bytes; w.r0 = r0; w.r1 = r1 < n_records ? r1 : n_records; w.k = m->k;
         w.windows = m->windows.p;
         hipLaunchKernelGGL(rmh_windows_kernel, dim3(grid_for(w.r1 - w.r0, 1, resident)), dim3(kThreads), 0, st, w);
@@ -688,16 +633,16 @@ int run(Handle *m, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes
     uint32_t *list = nullptr, *next = m->list_a.p;
     uint64_t n_list = n_records;
     while (m->num && n_list) {
-        m->h_stage[0] = 0; m->h_stage[1] = kAll;
-        CT_HIPCHK(hipMemcpyAsync(m->ctr.p + kCtrList, m->h_stage, 2 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        m->h_stage.p[0] = 0; m->h_stage.p[1] = kAll;
+        CT_HIPCHK(hipMemcpyAsync(m->ctr.p + kCtrList, m->h_stage.p, 2 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         AcceptArgs q;
         q.list = list; q.n = n_list; q.num = m->num; q.start = m->start.p; q.lo = m->lo.p; q.tau = m->tau.p; q.next = next; q.ctr = m->ctr.p;
         hipLaunchKernelGGL(rmh_accept_kernel, dim3(blocks_for(n_list)), dim3(kThreads), 0, st, q);
         CT_HIPCHK(hipGetLastError());
-        if ((rc = read_words(m, m->ctr.p + kCtrList, 2))) return rc;
-        n_list = m->h_stage[0];
+        if ((rc = m->h_stage.read(st, m->ctr.p + kCtrList, 2))) return rc;
+        n_list = m->h_stage.p[0];
         if (n_list == 0) break;
-        const uint64_t from = m->h_stage[1];
+        const uint64_t from = m->h_stage.p[1];
         if (m->n_rounds == 1) m->n_retried = n_list;
         m->n_rounds++;
         list = next;
@@ -744,8 +689,7 @@ int ntk_record_minhash_create(ntk_ctx *ctx, uint32_t k, uint32_t path, uint64_t 
     if (rc) { delete m; return rc; }
     m->num = num; m->scaled = scaled; m->max_hash = scaled ? kAll / scaled : kAll; m->limit = num ? num : kAll;
     m->cap = buffer_entries;
-    const hipError_t e = hipHostMalloc((void **)&m->h_stage, kCtrWords * sizeof(uint64_t), hipHostMallocDefault);
-    if (e != hipSuccess) { rc = alloc_status(e); delete m; return rc; }
+    if ((rc = m->h_stage.alloc(kCtrWords))) { delete m; return rc; }
     *out = m;
     return NTK_OK;
 }
@@ -767,7 +711,7 @@ void ntk_record_minhash_destroy(ntk_record_minhash *m)
 {
     if (!m) return;
     (void)ntk_record_minhash_trim(m);
-    if (m->h_stage) (void)hipHostFree(m->h_stage);
+    m->h_stage.release();
     (void)hipGetLastError();
     delete m;
 }
@@ -830,7 +774,8 @@ int ntk_record_minhash_stats(ntk_record_minhash *m, struct ntk_record_minhash_st
     out->num = m->num; out->scaled = m->scaled;
     out->buffer_entries = m->cap;
     out->n_rounds = m->n_rounds; out->n_retried_records = m->n_retried; out->n_redone = m->n_redone;
-    out->device_bytes = m->bytes + m->scratch.bytes * 8 + m->scratch.bytes / 16 * 4;   // values, and two planes of 2 B per 16 bases
+    out->device_bytes = m->scratch.device_bytes();   // values, and two planes of 2 B per 16 bases
+    m->each_array([&](const auto &d) { out->device_bytes += d.bytes(); });
     out->k = m->k; out->path = m->path;
     return NTK_OK;
 }

@@ -1,7 +1,7 @@
 // HyperLogLog sketch of the distinct k-mers of device batches (include/needletail_amd_sketch.h): the first pass that sizes a count
 // table.  A consumer of the core's public ABI like the two tables, with their two routes: k <= 32 reads the values
 // ntk_materialize_device_quality emits (every path's keys are the core's by construction), k = 33..63 walks the batch bytes as the
-// wide table's count kernel does (walk_lane_run below).
+// wide table's count kernel does (walk_lane_run of ntk_wide_walk.hpp).
 //
 // THE ONE PLACE that fixes hash, index and rank is sketch_slot / sketch_rank below (fmix64 is ntk_consumer.hpp's, the tables'
 // hash); the header states them and tests/_sketch_model.py restates them.
@@ -14,6 +14,7 @@
 // DESIGN.md section 12.
 #include "../../include/needletail_amd_sketch.h"
 #include "ntk_consumer.hpp"
+#include "ntk_wide_walk.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -26,12 +27,8 @@ constexpr uint32_t kRankMax = 64 - kP + 1;               // 51: every one of the
 constexpr uint64_t kXor = 0x9E3779B97F4A7C15ull;         // C: key 0 (AAA...A) must not hash to 0
 constexpr int kSketchThreads = 1024;                     // 16 waves per block: two blocks (2 x 64 KiB of LDS) keep 8 waves per SIMD
 constexpr uint32_t kPerLane = 4;                         // window ends per lane and round of sk_update_kernel (loads in flight)
-constexpr uint32_t kKMax = 63;
-constexpr uint32_t kLaneRun = 64;                        // window ends per lane of sk_wide_update_kernel, as wt_count_kernel
-constexpr uint32_t kPrime = 64;                          // bytes each lane reads before its first end (>= kKMax - 1, a multiple of 16)
 
 static_assert(kRankMax == NTK_SKETCH_MAX_RANK && kXor == NTK_SKETCH_XOR, "the header states the sketch's constants");
-static_assert(kPrime >= kKMax - 1, "lane geometry");
 static_assert(kRegisters % kSketchThreads == 0, "the clear and the flush walk the registers in whole rounds");
 
 __host__ __device__ inline uint64_t sketch_hash(uint64_t key) { return fmix64(key ^ kXor); }
@@ -104,53 +101,6 @@ __global__ __launch_bounds__(kSketchThreads) void sk_update_kernel(UpdateArgs a)
     flush(cells, a.regs, windows, a.n_windows);
 }
 
-// The byte walk of wt_count_kernel (ntk_wide_count.hip), restated: the same geometry and the same base, break and quality rules, with the
-// key handed to `emit` instead of the table.  The lane owns the window ends [first_end, first_end + kRun): it reads the kLead bytes before its first end (kLead >= k - 1, a
-// multiple of 16) and its own kRun bytes in 16-byte loads, rolls the forward and reverse-complement words (two u64 each: hi = the
-// first k - 32 bases, lo = the last 32) over all of them, and calls emit(hi, lo) with min(forward, reverse complement) of every window
-// that ends in its run after k base bytes in a row.  Bases are ACGTacgtUu with a quality byte >= cutoff (qual == nullptr: no mask).
-// A load is issued only for a 16-byte block that starts in [0, n_bytes) (the layout makes round_up(n_bytes, 16) readable), and a byte
-// at or past n_bytes is a break.
-template <uint32_t kRun, uint32_t kLead, class Emit>
-__device__ __forceinline__ void walk_lane_run(const uint8_t *seq, const uint8_t *qual, uint64_t n_bytes, uint32_t k, uint32_t cutoff,
-                                     uint64_t first_end, Emit emit)
-{
-    static_assert(kLead % 16 == 0 && kRun % 16 == 0, "lane geometry");
-    const uint32_t hi_bits = 2 * k - 64, rc_shift = 2 * k - 66;
-    const uint64_t hi_mask = ((uint64_t)1 << hi_bits) - 1;
-    uint64_t fh = 0, fl = 0, rh = 0, rl = 0;
-    uint32_t run = 0;
-#pragma unroll 1
-    for (uint32_t blk = 0; blk < (kLead + kRun) / 16; blk++) {
-        // 16 bytes starting at first_end - kLead + 16 * blk (before 0 or at / past n_bytes: breaks)
-        const uint64_t at = first_end + 16 * blk;   // = the block's start + kLead
-        uint4 s = make_uint4(0, 0, 0, 0), q = make_uint4(~0u, ~0u, ~0u, ~0u);
-        if (at >= kLead && at - kLead < n_bytes) {
-            s = *reinterpret_cast<const uint4 *>(seq + (at - kLead));
-            if (qual) q = *reinterpret_cast<const uint4 *>(qual + (at - kLead));
-        }
-#pragma unroll 1
-        for (uint32_t j = 0; j < 16; j++) {
-            const uint32_t b = s.x & 0xFF, qb = q.x & 0xFF;
-            s.x = (s.x >> 8) | (s.y << 24); s.y = (s.y >> 8) | (s.z << 24); s.z = (s.z >> 8) | (s.w << 24); s.w >>= 8;
-            q.x = (q.x >> 8) | (q.y << 24); q.y = (q.y >> 8) | (q.z << 24); q.z = (q.z >> 8) | (q.w << 24); q.w >>= 8;
-            const uint64_t pos_plus = at + j;   // the byte's position + kLead
-            const uint32_t l = b | 0x20;        // ACGTU / acgtu -> lower case
-            const bool base = (l == 'a' || l == 'c' || l == 'g' || l == 't' || l == 'u') && qb >= cutoff && pos_plus - kLead < n_bytes;
-            const uint64_t c = ((b >> 1) ^ (b >> 2)) & 3;   // A 0, C 1, G 2, T / U 3 in either case
-            fh = ((fh << 2) | (fl >> 62)) & hi_mask;
-            fl = (fl << 2) | c;
-            rl = (rl >> 2) | (rh << 62);
-            rh = (rh >> 2) | ((3 - c) << rc_shift);
-            run = base ? run + 1 : 0;
-            if (run >= k && pos_plus >= first_end + kLead) {
-                const bool fwd = fh < rh || (fh == rh && fl <= rl);
-                emit(fwd ? fh : rh, fwd ? fl : rl);
-            }
-        }
-    }
-}
-
 struct WideArgs {
     const uint8_t *seq, *qual;   // qual: nullptr = no mask
     uint64_t n_bytes;            // windows ending in [0, n_bytes) are taken; no byte at or past it is a base
@@ -197,10 +147,10 @@ void evaluate(const uint64_t *c, uint64_t n_windows, uint32_t k, struct ntk_kmer
 }  // namespace
 
 struct ntk_kmer_sketch : Consumer {
-    uint32_t *d_regs = nullptr;       // the registers as the kernels keep them: one 32-bit word each
-    uint64_t *d_windows = nullptr;    // k-mers added by add_device since reset
+    DeviceArray<uint32_t> d_regs;     // the registers as the kernels keep them: one 32-bit word each
+    DeviceArray<uint64_t> d_windows;  // k-mers added by add_device since reset
     uint64_t merged_windows = 0;      // k-mers of the sketches merged in since reset
-    uint32_t *h_stage = nullptr;      // pinned: kRegisters words, then the window count (two words)
+    Pinned<uint32_t> h_stage;         // kRegisters words, then the window count (two words)
     MaterialiseScratch scratch;       // k <= 32 only
 };
 
@@ -210,11 +160,10 @@ namespace {
 int read_back(ntk_kmer_sketch *s, uint64_t *windows)
 {
     CT_HIPCHK(hipSetDevice(s->device));
-    CT_HIPCHK(hipMemcpyAsync(s->h_stage, s->d_regs, kRegisters * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    CT_HIPCHK(hipMemcpyAsync(s->h_stage + kRegisters, s->d_windows, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-    CT_HIPCHK(hipStreamSynchronize(s->stream));
-    if (windows) memcpy(windows, s->h_stage + kRegisters, sizeof(uint64_t));
-    return NTK_OK;
+    CT_HIPCHK(hipMemcpyAsync(s->h_stage.p + kRegisters, s->d_windows.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+    const int rc = s->h_stage.read(s->stream, s->d_regs.p, kRegisters);
+    if (!rc && windows) memcpy(windows, s->h_stage.p + kRegisters, sizeof(uint64_t));
+    return rc;
 }
 
 }  // namespace
@@ -232,11 +181,11 @@ int ntk_kmer_sketch_create(ntk_ctx *ctx, uint32_t k, uint32_t path, ntk_kmer_ske
     if (!s) return NTK_ERR_NOMEM;
     int rc = s->bind(ctx, k, path);
     if (rc) { delete s; return rc; }
-    hipError_t e = hipMalloc((void **)&s->d_regs, kRegisters * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_windows, sizeof(uint64_t));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_stage, (kRegisters + 2) * sizeof(uint32_t), hipHostMallocDefault);
-    rc = e == hipSuccess ? ntk_kmer_sketch_reset(s) : alloc_status(e);
-    if (rc) { ntk_kmer_sketch_destroy(s); return rc; }
+    if ((rc = s->d_regs.ensure(s->stream, kRegisters, grow_exact)) || (rc = s->d_windows.ensure(s->stream, 1, grow_exact)) ||
+        (rc = s->h_stage.alloc(kRegisters + 2)) || (rc = ntk_kmer_sketch_reset(s))) {
+        ntk_kmer_sketch_destroy(s);
+        return rc;
+    }
     *out = s;
     return NTK_OK;
 }
@@ -247,9 +196,8 @@ void ntk_kmer_sketch_destroy(ntk_kmer_sketch *s)
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
     s->scratch.release();
-    if (s->d_regs) (void)hipFree(s->d_regs);
-    if (s->d_windows) (void)hipFree(s->d_windows);
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
+    s->d_regs.release(); s->d_windows.release();
+    s->h_stage.release();
     (void)hipGetLastError();
     delete s;
 }
@@ -258,8 +206,8 @@ int ntk_kmer_sketch_reset(ntk_kmer_sketch *s)
 {
     if (!s) return NTK_ERR_BAD_ARG;
     CT_HIPCHK(hipSetDevice(s->device));
-    CT_HIPCHK(hipMemsetAsync(s->d_regs, 0, kRegisters * sizeof(uint32_t), s->stream));
-    CT_HIPCHK(hipMemsetAsync(s->d_windows, 0, sizeof(uint64_t), s->stream));
+    CT_HIPCHK(hipMemsetAsync(s->d_regs.p, 0, kRegisters * sizeof(uint32_t), s->stream));
+    CT_HIPCHK(hipMemsetAsync(s->d_windows.p, 0, sizeof(uint64_t), s->stream));
     s->merged_windows = 0;
     return NTK_OK;
 }
@@ -274,10 +222,8 @@ int ntk_kmer_sketch_add_device(ntk_kmer_sketch *s, const uint8_t *d_seq, const u
     if (s->k > 32) {
         WideArgs a;
         a.seq = d_seq; a.n_bytes = n_bytes; a.k = s->k;
-        a.cutoff = (p->flags >> 8) & 0xFF;
-        a.qual = a.cutoff ? d_qual : nullptr;
-        if (!a.qual) a.cutoff = 0;
-        a.regs = s->d_regs; a.n_windows = s->d_windows;
+        set_quality(a, p, d_qual);
+        a.regs = s->d_regs.p; a.n_windows = s->d_windows.p;
         const uint64_t runs = (n_bytes + kLaneRun - 1) / kLaneRun;
         hipLaunchKernelGGL(sk_wide_update_kernel, dim3(grid_for(runs, kSketchThreads, resident)), dim3(kSketchThreads), 0, s->stream, a);
         CT_HIPCHK(hipGetLastError());
@@ -286,9 +232,9 @@ int ntk_kmer_sketch_add_device(ntk_kmer_sketch *s, const uint8_t *d_seq, const u
     // of every chunk only the windows ending at or after its start are taken - the max would not mind a window twice, n_windows does
     return for_each_chunk(*s, s->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         UpdateArgs a;
-        a.values = s->scratch.d_values; a.valid16 = s->scratch.d_valid16;
+        a.values = s->scratch.d_values.p; a.valid16 = s->scratch.d_valid16.p;
         a.first = c.skip(); a.n = c.len();
-        a.regs = s->d_regs; a.n_windows = s->d_windows;
+        a.regs = s->d_regs.p; a.n_windows = s->d_windows.p;
         const uint64_t rounds = (a.n - a.first + kPerLane - 1) / kPerLane;
         hipLaunchKernelGGL(sk_update_kernel, dim3(grid_for(rounds, kSketchThreads, resident)), dim3(kSketchThreads), 0, s->stream, a);
         CT_HIPCHK(hipGetLastError());
@@ -301,7 +247,7 @@ int ntk_kmer_sketch_registers(ntk_kmer_sketch *s, uint8_t *regs)
     if (!s || !regs) return NTK_ERR_BAD_ARG;
     int rc = read_back(s, nullptr);
     if (rc) return rc;
-    for (uint32_t j = 0; j < kRegisters; j++) regs[j] = (uint8_t)s->h_stage[j];
+    for (uint32_t j = 0; j < kRegisters; j++) regs[j] = (uint8_t)s->h_stage.p[j];
     return NTK_OK;
 }
 
@@ -313,9 +259,8 @@ int ntk_kmer_sketch_merge(ntk_kmer_sketch *s, const uint8_t *regs, uint64_t n_wi
     int rc = read_back(s, nullptr);
     if (rc) return rc;
     for (uint32_t j = 0; j < kRegisters; j++)
-        if (regs[j] > s->h_stage[j]) s->h_stage[j] = regs[j];
-    CT_HIPCHK(hipMemcpyAsync(s->d_regs, s->h_stage, kRegisters * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    CT_HIPCHK(hipStreamSynchronize(s->stream));   // the stage is free again
+        if (regs[j] > s->h_stage.p[j]) s->h_stage.p[j] = regs[j];
+    if ((rc = s->h_stage.write(s->stream, s->d_regs.p, kRegisters))) return rc;
     s->merged_windows += n_windows;
     return NTK_OK;
 }
@@ -326,7 +271,7 @@ int ntk_kmer_sketch_estimate(ntk_kmer_sketch *s, struct ntk_kmer_sketch_estimate
     uint64_t windows = 0, c[kRankMax + 1] = {};
     int rc = read_back(s, &windows);
     if (rc) return rc;
-    for (uint32_t j = 0; j < kRegisters; j++) c[s->h_stage[j] <= kRankMax ? s->h_stage[j] : kRankMax]++;
+    for (uint32_t j = 0; j < kRegisters; j++) c[s->h_stage.p[j] <= kRankMax ? s->h_stage.p[j] : kRankMax]++;
     evaluate(c, windows + s->merged_windows, s->k, out);
     out->k = s->k; out->path = s->path;
     return NTK_OK;

@@ -335,59 +335,24 @@ __global__ __launch_bounds__(kCopyThreads) void rt_copy_long_kernel(CopyArgs a)
 struct ntk_read_trim : Consumer {        // k and path: the table's
     ntk_kmer_table *table = nullptr;   // borrowed
     MaterialiseScratch scratch;        // of one chunk
-    uint64_t chunk_bases = 0;          // bases d_counts holds (a multiple of 16, at most kChunkBases)
-    uint64_t *d_counts = nullptr;      // 8 B per base of one chunk
-    uint64_t plane_words = 0;          // words each plane holds
-    uint64_t *d_solid = nullptr, *d_valid = nullptr;
+    DeviceArray<uint64_t> d_counts;    // 8 B per base of one chunk (a multiple of 16 bases, at most kChunkBases)
+    DeviceArray<uint64_t> d_solid, d_valid;   // the planes: one word per 64 bases of the batch each
     // the compaction's
-    uint64_t scan_items = 0, scan_tmp_bytes = 0, long_cap = 0;
-    ScanItem *d_scan = nullptr;
-    void *d_scan_tmp = nullptr;
-    uint64_t *d_long = nullptr;        // [0]: the number of long records, then their indices
+    DeviceArray<ScanItem> d_scan;
+    DeviceArray<char> d_scan_tmp;
+    DeviceArray<uint64_t> d_long;      // [0]: the number of long records, then their indices
 
     void release_all()
     {
         scratch.release();
-        for (void *q : {(void *)d_counts, (void *)d_solid, (void *)d_valid, (void *)d_scan, d_scan_tmp, (void *)d_long})
-            if (q) (void)hipFree(q);
-        d_counts = d_solid = d_valid = d_long = nullptr; d_scan = nullptr; d_scan_tmp = nullptr;
-        chunk_bases = plane_words = scan_items = scan_tmp_bytes = long_cap = 0;
-    }
-
-    // a device buffer of at least `need` units of `unit` bytes: kept when it is large enough, replaced otherwise (the stream is idle by then)
-    template <class T>
-    int grow(T *&p, uint64_t &have, uint64_t need, uint64_t unit)
-    {
-        if (need <= have) return NTK_OK;
-        CT_HIPCHK(hipStreamSynchronize(stream));
-        if (p) (void)hipFree(p);
-        p = nullptr; have = 0;
-        const hipError_t e = hipMalloc((void **)&p, need * unit);
-        if (e != hipSuccess) { p = nullptr; return alloc_status(e); }
-        have = need;
-        return NTK_OK;
+        d_counts.release(); d_solid.release(); d_valid.release();
+        d_scan.release(); d_scan_tmp.release(); d_long.release();
     }
 };
 
 namespace {
 
 uint64_t planes_words(uint64_t n_bytes) { return (n_bytes + 63) / 64 + 1; }
-
-int ensure_planes(ntk_read_trim *t, uint64_t n_bytes)
-{
-    const uint64_t need = planes_words(n_bytes);
-    if (need <= t->plane_words) return NTK_OK;
-    uint64_t have = t->plane_words, have2 = t->plane_words;
-    int rc = t->grow(t->d_solid, have, need, sizeof(uint64_t));
-    if (!rc) rc = t->grow(t->d_valid, have2, need, sizeof(uint64_t));
-    t->plane_words = rc ? 0 : need;
-    if (rc) {
-        for (void *q : {(void *)t->d_solid, (void *)t->d_valid})
-            if (q) (void)hipFree(q);
-        t->d_solid = t->d_valid = nullptr;
-    }
-    return rc;
-}
 
 }  // namespace
 
@@ -435,20 +400,21 @@ int ntk_read_trim_run_device(ntk_read_trim *t, const uint8_t *d_seq, const uint8
     if ((rc = check_batch_pointers(d_seq, d_qual))) return rc;
     if (!d_offsets || !d_rows || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_rows & 7)) return NTK_ERR_BAD_ARG;
     CT_HIPCHK(hipSetDevice(t->device));
-    rc = t->grow(t->d_counts, t->chunk_bases, (chunk_bases(n_bytes) + 15) & ~(uint64_t)15, sizeof(uint64_t));
-    if (!rc) rc = ensure_planes(t, n_bytes);
-    if (rc) return rc;
+    if ((rc = t->d_counts.ensure(t->stream, (chunk_bases(n_bytes) + 15) & ~(uint64_t)15, grow_exact)) ||
+        (rc = t->d_solid.ensure(t->stream, planes_words(n_bytes), grow_exact)) ||
+        (rc = t->d_valid.ensure(t->stream, planes_words(n_bytes), grow_exact)))
+        return rc;
     // the counts of a chunk are turned into plane words before the next chunk's replace them
     rc = for_each_chunk(*t, t->scratch, d_seq, d_qual, n_bytes, p, [&](const Chunk &c) -> int {
         // values at invalid positions are undefined: looking them up is a bounded read-only probe, and the valid bit drops their counts.
         // An incomplete table fails here, on the first chunk, before any row is written.  Synchronises.
-        const int rc = ntk_kmer_table_lookup_device(t->table, t->scratch.d_values + c.skip(), c.end - c.start, t->d_counts);
+        const int rc = ntk_kmer_table_lookup_device(t->table, t->scratch.d_values.p + c.skip(), c.end - c.start, t->d_counts.p);
         if (rc) return rc;
         CT_HIPCHK(hipSetDevice(t->device));
         SolidArgs g;
-        g.counts = t->d_counts; g.valid16 = t->scratch.d_valid16 + c.skip() / 16;
+        g.counts = t->d_counts.p; g.valid16 = t->scratch.d_valid16.p + c.skip() / 16;
         g.n = c.end - c.start; g.min_count = min_count ? min_count : 1;
-        g.solid = t->d_solid + c.start / 64; g.valid = t->d_valid + c.start / 64;
+        g.solid = t->d_solid.p + c.start / 64; g.valid = t->d_valid.p + c.start / 64;
         hipLaunchKernelGGL(rt_solid_kernel, dim3(grid_for(g.n, 64 * kSolidRounds * (kSolidThreads / 64), (unsigned)t->n_cu * 8)),
                            dim3(kSolidThreads), 0, t->stream, g);
         CT_HIPCHK(hipGetLastError());
@@ -456,7 +422,7 @@ int ntk_read_trim_run_device(ntk_read_trim *t, const uint8_t *d_seq, const uint8
     });
     if (rc) return rc;
     IntervalArgs g;
-    g.solid = t->d_solid; g.valid = t->d_valid; g.offsets = d_offsets;
+    g.solid = t->d_solid.p; g.valid = t->d_valid.p; g.offsets = d_offsets;
     g.n_bytes = n_bytes; g.n_records = n_records; g.min_length = min_length;
     g.k = t->k; g.prefix = mode == NTK_TRIM_PREFIX;
     g.rows = d_rows;
@@ -490,20 +456,14 @@ int ntk_read_trim_compact_device(ntk_read_trim *t, const uint8_t *d_seq, const u
     // the exclusive scan of what every record writes; item n_records is the total
     const Batch b{d_offsets, d_rows, n_bytes, n_records};
     auto items = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), KeptItem{b});
-    size_t tmp_bytes = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp_bytes, items, (ScanItem *)nullptr, ScanItem{0, 0}, n_records + 1, ScanAdd(), t->stream) !=
-        hipSuccess) {
-        (void)hipGetLastError();
-        return NTK_ERR_HIP;
-    }
-    int rc = t->grow(t->d_scan, t->scan_items, n_records + 1, sizeof(ScanItem));
-    if (!rc) rc = t->grow(t->d_scan_tmp, t->scan_tmp_bytes, tmp_bytes ? tmp_bytes : 1, 1);
-    if (!rc) rc = t->grow(t->d_long, t->long_cap, (n_bytes >> 14) + 2, sizeof(uint64_t));
+    int rc = t->d_scan.ensure(t->stream, n_records + 1, grow_exact);
+    if (!rc) rc = t->d_long.ensure(t->stream, (n_bytes >> 14) + 2, grow_exact);
+    if (!rc) rc = with_tmp(t->d_scan_tmp, t->stream, grow_exact, [&](void *tmp, size_t &tmp_bytes) {
+        return rocprim::exclusive_scan(tmp, tmp_bytes, items, t->d_scan.p, ScanItem{0, 0}, n_records + 1, ScanAdd(), t->stream);
+    });
     if (rc) return rc;
-    tmp_bytes = t->scan_tmp_bytes;
-    CT_HIPCHK(rocprim::exclusive_scan(t->d_scan_tmp, tmp_bytes, items, t->d_scan, ScanItem{0, 0}, n_records + 1, ScanAdd(), t->stream));
     ScanItem total{0, 0};
-    CT_HIPCHK(hipMemcpyAsync(&total, t->d_scan + n_records, sizeof total, hipMemcpyDeviceToHost, t->stream));
+    CT_HIPCHK(hipMemcpyAsync(&total, t->d_scan.p + n_records, sizeof total, hipMemcpyDeviceToHost, t->stream));
     CT_HIPCHK(hipStreamSynchronize(t->stream));
     *out_n_bytes = total.bytes;
     *out_n_records = total.records;
@@ -516,12 +476,12 @@ int ntk_read_trim_compact_device(ntk_read_trim *t, const uint8_t *d_seq, const u
     }
     if (!d_out_seq || !d_out_offsets || !d_out_source) return NTK_ERR_BAD_ARG;   // a capacity without its array
     CopyArgs g;
-    g.b = b; g.scan = t->d_scan;
+    g.b = b; g.scan = t->d_scan.p;
     g.src_readable = (n_bytes + 15) & ~(uint64_t)15;
     g.out_offsets = d_out_offsets; g.out_source = d_out_source;
     g.total_bytes = total.bytes; g.total_records = total.records;
-    g.n_long = t->d_long; g.long_list = t->d_long + 1; g.long_cap = t->long_cap - 1;
-    CT_HIPCHK(hipMemsetAsync(t->d_long, 0, sizeof(uint64_t), t->stream));
+    g.n_long = t->d_long.p; g.long_list = t->d_long.p + 1; g.long_cap = t->d_long.cap - 1;
+    CT_HIPCHK(hipMemsetAsync(t->d_long.p, 0, sizeof(uint64_t), t->stream));
     for (int aux = 0; aux < (d_aux ? 2 : 1); aux++) {
         g.src = aux ? d_aux : d_seq; g.dst = aux ? d_out_aux : d_out_seq;
         g.aux = (uint32_t)aux; g.first = !aux;

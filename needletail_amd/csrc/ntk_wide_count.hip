@@ -198,12 +198,12 @@ __global__ __launch_bounds__(kThreads) void wt_lookup_kernel(Table t, uint32_t k
 }  // namespace
 
 struct ntk_wide_table : TableCore {
-    uint64_t *d_hi = nullptr, *d_lo = nullptr;
+    DeviceArray<uint64_t> d_hi, d_lo;
 };
 
 namespace {
 
-Table table_of(const ntk_wide_table *t) { return Table{t->d_hi, t->d_lo, t->d_counts, t->slots - 1, t->probe_max}; }
+Table table_of(const ntk_wide_table *t) { return Table{t->d_hi.p, t->d_lo.p, t->d_counts.p, t->slots - 1, t->probe_max}; }
 
 }  // namespace
 
@@ -230,14 +230,14 @@ int ntk_wide_table_create(ntk_ctx *ctx, uint32_t k, uint32_t path, uint64_t capa
 void ntk_wide_table_destroy(ntk_wide_table *t)
 {
     if (!t) return;
-    t->release({t->d_hi, t->d_lo});
+    t->release({&t->d_hi, &t->d_lo});
     delete t;
 }
 
 int ntk_wide_table_reset(ntk_wide_table *t)
 {
     if (!t) return NTK_ERR_BAD_ARG;
-    return t->reset({t->d_hi, t->d_lo}, kStWords);
+    return t->reset({&t->d_hi, &t->d_lo}, kStWords);
 }
 
 int ntk_wide_table_count_device(ntk_wide_table *t, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes, const ntk_params *p)
@@ -248,10 +248,8 @@ int ntk_wide_table_count_device(ntk_wide_table *t, const uint8_t *d_seq, const u
     CT_HIPCHK(hipSetDevice(t->device));
     CountArgs a;
     a.seq = d_seq; a.n_bytes = n_bytes; a.k = t->k;
-    a.cutoff = (p->flags >> 8) & 0xFF;
-    a.qual = a.cutoff ? d_qual : nullptr;
-    if (!a.qual) a.cutoff = 0;
-    a.t = table_of(t); a.stats = t->d_stats;
+    set_quality(a, p, d_qual);
+    a.t = table_of(t); a.stats = t->d_stats.p;
     const uint64_t runs = (n_bytes + kLaneRun - 1) / kLaneRun;
     hipLaunchKernelGGL(wt_count_kernel, dim3(grid_for(runs, kThreads, (unsigned)t->n_cu * 8)), dim3(kThreads), 0, t->stream, a);
     CT_HIPCHK(hipGetLastError());
@@ -279,7 +277,7 @@ int ntk_wide_table_extract_device(ntk_wide_table *t, uint64_t min_count, uint64_
     int rc = t->read_complete(w, kStWords);
     if (rc) return rc;
     if (min_count == 0) min_count = 1;
-    rc = t->extract_offsets(t->d_hi, min_count, &need);
+    rc = t->extract_offsets(t->d_hi.p, min_count, &need);
     if (rc) return rc;
     *n = need;
     if (need > cap) return NTK_ERR_CAPACITY;
@@ -289,8 +287,8 @@ int ntk_wide_table_extract_device(ntk_wide_table *t, uint64_t min_count, uint64_
     return t->scatter_sort<WideKey>(
         need,
         [&](WideKey *tk, uint64_t *tc) {
-            hipLaunchKernelGGL(wt_extract_scatter_kernel, dim3((unsigned)t->extract_blocks()), dim3(kThreads), 0, t->stream, t->d_hi,
-                               t->d_lo, t->d_counts, t->slots, min_count, t->d_offsets, tk, tc);
+            hipLaunchKernelGGL(wt_extract_scatter_kernel, dim3((unsigned)t->extract_blocks()), dim3(kThreads), 0, t->stream, t->d_hi.p,
+                               t->d_lo.p, t->d_counts.p, t->slots, min_count, t->d_offsets.p, tk, tc);
         },
         // the keys are < 2^(2k) as hi * 2^64 + lo: a radix sort on the low 2k bits of the pair orders them
         [&](void *tmp, size_t &tmp_bytes, WideKey *tk, uint64_t *tc) {
@@ -304,7 +302,7 @@ int ntk_wide_table_spectrum(ntk_wide_table *t, uint64_t *hist, uint32_t n_bins)
     if (!t || !hist || n_bins < 2 || n_bins > kMaxBins) return NTK_ERR_BAD_ARG;
     uint64_t w[kStWords];
     const int rc = t->read_complete(w, kStWords);
-    return rc ? rc : t->spectrum(t->d_hi, hist, n_bins);
+    return rc ? rc : t->spectrum(t->d_hi.p, hist, n_bins);
 }
 
 int ntk_wide_table_lookup_device(ntk_wide_table *t, const uint64_t *d_queries, uint64_t n, uint64_t *d_counts)

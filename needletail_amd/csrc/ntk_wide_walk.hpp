@@ -1,9 +1,9 @@
 // The byte walk of two-word keys (k = 33..63), for libraries that hand every canonical key of a device batch to a functor.
 //
-// This is wt_count_kernel's walk (ntk_wide_count.hip) as ntk_sketch.hip restates it: the same lane geometry and the same base, break and
-// quality rules.  Those two sources keep their own copies - sharing the walker changed wt_count_kernel's schedule,
-// and the kernel sets of both libraries are pinned - so only the MinHash library (ntk_minhash.hip) includes this header, and
-// tests/test_minhash_abi.py holds its constants and per-byte rules to the other two.
+// This is wt_count_kernel's walk (ntk_wide_count.hip): the same lane geometry and the same base, break and quality rules.  That kernel
+// keeps its own inline copy - sharing the walker changed its schedule, and the kernel set of its library is
+// pinned - so there is one header, and wt_count_kernel's own: the sketch (ntk_sketch.hip) and the MinHash library (ntk_minhash.hip)
+// include this one, and tests/test_minhash_abi.py holds its constants and per-byte rules to ntk_wide_count.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

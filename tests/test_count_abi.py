@@ -22,6 +22,9 @@ CSRC = os.path.join(ROOT, "needletail_amd", "csrc")
 COMMON = os.path.join(CSRC, "ntk_count_common.hpp")   # what the narrow and the wide table share
 CONSUMER = os.path.join(CSRC, "ntk_consumer.hpp")     # what every library on the core's ABI shares
 CHUNKS = os.path.join(CSRC, "ntk_chunks.hpp")         # the chunk geometry
+# the memory layer of the scaffold (ntk_device_mem.hpp, which ntk_consumer.hpp includes): what it defines, and nobody else does
+MEM = os.path.join(CSRC, "ntk_device_mem.hpp")
+MEM_DEFS = (r"struct DeviceArray\b\s*\{", r"struct Pinned\b\s*\{", r"\bint\s+with_tmp\s*\(")
 # the six library sources
 SOURCES = [os.path.join(CSRC, f"ntk_{name}.hip") for name in ("count", "wide_count", "sketch", "abundance", "trim", "minhash")]
 
@@ -109,6 +112,10 @@ def test_the_shared_pieces_are_defined_once():
         assert re.search(rf"\b{name}\([^)]*\)\s*\{{", consumer), (name, "not defined in ntk_consumer.hpp")
         assert not re.search(rf"\b{name}\([^)]*\)\s*\{{", common), (name, "defined again in ntk_count_common.hpp")
     assert re.search(r"struct MaterialiseScratch \{", consumer) and '#include "ntk_consumer.hpp"' in common
+    mem = open(MEM).read()
+    assert '#include "ntk_device_mem.hpp"' in consumer
+    for pat in MEM_DEFS:
+        assert len(re.findall(pat, mem)) == 1 and not re.search(pat, consumer) and not re.search(pat, common), pat
     assert len(re.findall(kernel, common)) == 3 and not re.search(kernel, consumer)
     for path in SOURCES:
         src = open(path).read()
@@ -116,9 +123,23 @@ def test_the_shared_pieces_are_defined_once():
             assert not re.search(rf"\b{name}\([^)]*\)\s*\{{", src), (name, "defined again in", path)
         assert not re.search(kernel, src), ("an extract count / scan or spectrum kernel defined again in", path)
         assert not re.search(r"struct MaterialiseScratch\b", src), path
+        for pat in MEM_DEFS:
+            assert not re.search(pat, src), (pat, "defined again in", path)
         # the two tables take the shared pieces through their own header, the other four directly
         want = "ntk_count_common.hpp" if path in (HIP, WIDE_HIP) else "ntk_consumer.hpp"
         assert f'#include "{want}"' in src, path
+
+
+def test_only_the_memory_layer_and_the_core_allocate():
+    """Device and pinned memory of the consumer libraries is allocated and freed in ntk_device_mem.hpp alone: apart from it, only the
+    core's own sources (ntk_api.hip, ntk_fastx*, ntk_pgzip*) name the four calls, comments included."""
+    core = re.compile(r"ntk_api\.hip$|ntk_fastx|ntk_pgzip")
+    found = set()
+    for name in sorted(os.listdir(CSRC)):
+        if re.search(r"\.(?:hip|hpp|cpp|h)$", name) and re.search(r"hip(?:Host)?(?:Malloc|Free)\b", open(os.path.join(CSRC, name)).read()):
+            found.add(name)
+    assert "ntk_device_mem.hpp" in found
+    assert [f for f in found if f != "ntk_device_mem.hpp" and not core.search(f)] == []
 
 
 def test_no_device_is_a_loud_error():

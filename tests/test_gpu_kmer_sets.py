@@ -301,6 +301,51 @@ def test_capacity_query_exact_fit_and_one_short(ctx, kw):
             assert bool((keys[kw * need:] == sentinel).all()) and bool((counts[need:] == sentinel).all()), "nothing past the result"
 
 
+def _union_sum(a, ca, b, cb):
+    keys = np.union1d(a, b)
+    counts = np.zeros(keys.size, dtype=np.uint64)
+    counts[np.searchsorted(keys, a)] += ca
+    counts[np.searchsorted(keys, b)] += cb
+    return keys, counts
+
+
+def test_scratch_regrows_on_one_handle_and_after_release(ctx):
+    """One handle joins lists of 100 keys, then lists of more than 1024 tiles (the tile arrays' first size), then - its scratch released -
+    lists of 100 again.  Every union is numpy's (the small ones the model's too), and the scratch a grown handle holds is what a fresh one
+    allocates for the same call."""
+    n_big = 1024 * T // 2 + 1
+    assert (2 * n_big + T - 1) // T == 1025
+    rng = np.random.default_rng(0xB17)
+    lists = []
+    for n in (100, n_big):
+        pool = np.unique(rng.integers(0, 1 << 63, 3 * n, dtype=np.uint64))
+        a, b = np.sort(rng.choice(pool, n, replace=False)), np.sort(rng.choice(pool, n, replace=False))
+        lists.append((a, rng.integers(1, 300, n, dtype=np.uint64), b, rng.integers(1, 12, n, dtype=np.uint64)))
+    keys = torch.empty(2 * n_big, dtype=torch.int64, device="cuda")
+    counts = torch.empty(2 * n_big, dtype=torch.int64, device="cuda")
+
+    def union_on(h, a, ca, b, cb, what):
+        want_k, want_c = _union_sum(a, ca, b, cb)
+        with make(ctx, a, ca) as sa, make(ctx, b, cb) as sb:
+            assert _raw_apply(h, KM.UNION, KM.SUM, sa, sb, keys, counts, 2 * a.size) == (0, want_k.size), what
+        assert np.array_equal(keys[: want_k.size].cpu().numpy().view(np.uint64), want_k), what
+        assert np.array_equal(counts[: want_k.size].cpu().numpy().view(np.uint64), want_c), what
+        return h.stats()["device_bytes"]
+
+    small, big = lists
+    model_k, model_c = KM.as_list(KM.apply(KM.UNION, KM.SUM, KM.as_dict(small[0], small[1]), KM.as_dict(small[2], small[3])), 1)
+    numpy_k, numpy_c = _union_sum(*small)
+    assert np.array_equal(model_k, numpy_k) and np.array_equal(model_c, numpy_c) and 100 < numpy_k.size < 200
+    with make(ctx, small[0], small[1]) as h, make(ctx, small[0], small[1]) as fresh:
+        bytes_small = union_on(h, *small, "100")
+        bytes_big = union_on(h, *big, "big")
+        assert bytes_big > bytes_small
+        assert union_on(fresh, *big, "big, fresh") == bytes_big
+        h.release()
+        assert h.stats()["device_bytes"] < bytes_small
+        assert union_on(h, *small, "100 after release") == bytes_small
+
+
 def test_argument_checks(ctx):
     lib = KS.lib()
     keys, counts = ramp(100), cnt(100)

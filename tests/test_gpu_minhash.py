@@ -184,6 +184,29 @@ def test_overflow_and_redo(ctx, k, buffer_entries):
         assert mh.stats()["buffer_entries"] == M.BUFFER_DEFAULT
 
 
+@pytest.mark.parametrize("k", [21, 51])
+def test_one_handle_grows_across_calls_and_starts_over(ctx, k):
+    """One handle, three batches of about 200, 20 000 and 200 bases: the kept set, the runs, the merge's arrays and rocPRIM's temporary
+    storage, sized by the first batch, are all replaced by larger ones in the second call and used again, too large, by the third.  The
+    sketch is the model's on everything added so far after every call, and the last batch's alone after a reset."""
+    rng = np.random.default_rng(0x3C00 + k)
+    bufs = [pack([bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), n))]) for n in (200, 20_000, 200)]
+    keys = [oracle_keys(buf, k, BYTES, nt.PRE_NORMALIZE) for buf in bufs]
+    assert [len(v) for v in keys] == [200 - k + 1, 20_000 - k + 1, 200 - k + 1]
+    for kind in (dict(scaled=2), dict(num=64)):
+        with nt.KmerMinHash(k, BYTES, ctx=ctx, **kind) as mh:
+            for i, buf in enumerate(bufs):
+                mh.add_device(upload(buf), len(buf), nt.PRE_NORMALIZE)
+                st, _ = assert_minhash(mh, np.concatenate(keys[: i + 1]), (k, kind, "call", i))
+                if "scaled" in kind:   # every batch has hashes under a fixed threshold (a bottom-s threshold may let none of a batch in)
+                    assert st["n_merges"] >= i + 1
+            if "scaled" in kind:
+                assert st["n_kept"] > 20 * (200 - k + 1)   # far more than the first call's arrays held
+            mh.reset()
+            mh.add_device(upload(bufs[2]), len(bufs[2]), nt.PRE_NORMALIZE)
+            assert_minhash(mh, keys[2], (k, kind, "after reset"))
+
+
 # ---- 4. a tie at the threshold ------------------------------------------------------------------------------------------------------
 
 def test_a_tie_at_the_threshold(ctx):

@@ -18,6 +18,9 @@ SO = os.path.join(LIBDIR, "libneedletail_amd_kmer_sets.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_kmer_sets.h")
 CSRC = os.path.join(ROOT, "needletail_amd", "csrc")
 HIP, RULE_HPP, CONSUMER = (os.path.join(CSRC, f) for f in ("ntk_kmer_sets.hip", "ntk_kset_rule.hpp", "ntk_consumer.hpp"))
+# the memory layer of the scaffold (ntk_device_mem.hpp, which ntk_consumer.hpp includes): what it defines, and nobody else does
+MEM = os.path.join(CSRC, "ntk_device_mem.hpp")
+MEM_DEFS = (r"struct DeviceArray\b\s*\{", r"struct Pinned\b\s*\{", r"\bint\s+with_tmp\s*\(")
 GPU_TESTS = "test_gpu_kmer_sets.py"
 OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so",
               "libneedletail_amd_abundance.so", "libneedletail_amd_trim.so", "libneedletail_amd_minhash.so",
@@ -153,6 +156,11 @@ def test_the_shared_pieces_are_used_and_not_defined_again():
         assert re.search(rf"\b{name}\([^)]*\)\s*\{{", consumer), (name, "not defined in ntk_consumer.hpp")
         for text in (src, rule):
             assert not re.search(rf"\b{name}\([^)]*\)\s*\{{", text), (name, "defined again")
+    assert '#include "ntk_device_mem.hpp"' in consumer
+    for pat in MEM_DEFS:
+        assert len(re.findall(pat, open(MEM).read())) == 1, (pat, "not defined in ntk_device_mem.hpp")
+        for text in (src, rule):
+            assert not re.search(pat, text), (pat, "defined again")
     for text in (src, rule):
         assert not re.search(r"struct (?:MaterialiseScratch|Consumer)\b\s*\{", text)
         code = _no_comments(text)
@@ -160,7 +168,7 @@ def test_the_shared_pieces_are_used_and_not_defined_again():
         assert not re.search(r"\basm\b|__asm", code), "plain HIP C++"
         assert not re.search(r"\b(?:double|float)\b", code), "no floating point anywhere in the library"
     code = _no_comments(src)
-    for name in ("wave_sum", "add_agent", "block_sum_u32", "grid_for", "alloc_status"):
+    for name in ("wave_sum", "add_agent", "block_sum_u32", "grid_for", "with_tmp"):   # (alloc_status is used by the memory layer now)
         assert re.search(rf"\b{name}\(", code), name
     assert "h->bind(ctx, 0, 0)" in src and "rocprim::exclusive_scan" in src
     assert not re.search(r"needletail_amd_(?:count|wide_count)\.h", src), "it never touches a table"

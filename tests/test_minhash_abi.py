@@ -178,10 +178,11 @@ def test_minhash_constants_are_the_sketchs_and_the_models():
 
 
 def test_walker_header_is_the_two_sources_walk():
-    """ntk_wide_walk.hpp restates the walk of ntk_sketch.hip and ntk_wide_count.hip: the same lane run, lead, k range and per-byte rules.
-    Only the MinHash library includes it."""
+    """ntk_wide_walk.hpp restates the walk of ntk_wide_count.hip, which keeps its own: the same lane run, lead, k range and per-byte
+    rules.  The sketch's walk is the header's by construction: ntk_sketch.hip includes it and defines neither a walker nor the lane
+    geometry.  The MinHash library and the sketch include it, and nothing else does."""
     walk, sk, wide = open(WALK_HPP).read(), open(SKETCH_HIP).read(), open(WIDE_HIP).read()
-    for text in (walk, sk, wide):
+    for text in (walk, wide):
         assert int(re.search(r"kLaneRun = (\d+);", text).group(1)) == M.LANE_RUN
         assert int(re.search(r"kPrime = (\d+);", text).group(1)) == M.PRIME
         assert re.search(r"kKMax = (\d+);", text).group(1) == "63"
@@ -199,14 +200,16 @@ def test_walker_header_is_the_two_sources_walk():
              "rl = (rl >> 2) | (rh << 62);", "rh = (rh >> 2) | ((3 - c) << rc_shift);", "run = base ? run + 1 : 0;",
              "if (run >= k && pos_plus >= first_end + kLead) {", "const bool fwd = fh < rh || (fh == rh && fl <= rl);")
     for rule in rules:
-        for name, text in (("walk", walk), ("sketch", sk), ("wide", wide)):
+        for name, text in (("walk", walk), ("wide", wide)):
             assert rule in norm(text), (name, rule)
-    # the walker itself is the sketch's, character for character
-    body = lambda t: re.sub(r"\s+", " ", re.search(r"(template <uint32_t kRun, uint32_t kLead, class Emit>.*?\n\}\n)", t, re.S).group(1))
-    assert body(walk) == body(sk)
+    # the sketch walks with the header's walker and geometry: it includes the header and restates neither
+    assert '#include "ntk_wide_walk.hpp"' in sk and "walk_lane_run<kLaneRun, kPrime>(" in sk
+    assert not re.search(r"template <uint32_t kRun, uint32_t kLead, class Emit>", sk), "a walker defined again in ntk_sketch.hip"
+    assert not re.search(r"\bk(?:LaneRun|Prime|KMax)\s*=", sk), "the lane geometry stated again in ntk_sketch.hip"
+    assert len(re.findall(r"template <uint32_t kRun, uint32_t kLead, class Emit>", walk)) == 1
     users = [f for f in sorted(os.listdir(CSRC)) if "ntk_wide_walk.hpp" in open(os.path.join(CSRC, f), errors="replace").read()
              and f != "ntk_wide_walk.hpp" and f != "Makefile"]
-    assert users == ["ntk_minhash.hip"], users
+    assert users == ["ntk_minhash.hip", "ntk_sketch.hip"], users
 
 
 # ---- the model's algebra ------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,9 @@ SO = os.path.join(LIBDIR, "libneedletail_amd_minhash_set.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_minhash_set.h")
 CSRC = os.path.join(ROOT, "needletail_amd", "csrc")
 HIP, RANK_HPP, CONSUMER = (os.path.join(CSRC, f) for f in ("ntk_minhash_set.hip", "ntk_mhset_rank.hpp", "ntk_consumer.hpp"))
+# the memory layer of the scaffold (ntk_device_mem.hpp, which ntk_consumer.hpp includes): what it defines, and nobody else does
+MEM = os.path.join(CSRC, "ntk_device_mem.hpp")
+MEM_DEFS = (r"struct DeviceArray\b\s*\{", r"struct Pinned\b\s*\{", r"\bint\s+with_tmp\s*\(")
 GPU_TESTS = "test_gpu_minhash_set.py"
 OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so",
               "libneedletail_amd_abundance.so", "libneedletail_amd_trim.so", "libneedletail_amd_minhash.so")
@@ -139,6 +142,11 @@ def test_the_shared_pieces_are_used_and_not_defined_again():
         assert re.search(rf"\b{name}\([^)]*\)\s*\{{", consumer), (name, "not defined in ntk_consumer.hpp")
         for text in (src, rank):
             assert not re.search(rf"\b{name}\([^)]*\)\s*\{{", text), (name, "defined again")
+    assert '#include "ntk_device_mem.hpp"' in consumer
+    for pat in MEM_DEFS:
+        assert len(re.findall(pat, open(MEM).read())) == 1, (pat, "not defined in ntk_device_mem.hpp")
+        for text in (src, rank):
+            assert not re.search(pat, text), (pat, "defined again")
     for text in (src, rank):
         assert not re.search(r"struct (?:MaterialiseScratch|Consumer)\b\s*\{", text)
         assert "ntk_wide_walk.hpp" not in text and "needletail_amd_minhash.h" not in text

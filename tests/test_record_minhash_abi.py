@@ -19,6 +19,9 @@ SO = os.path.join(LIBDIR, "libneedletail_amd_record_minhash.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_record_minhash.h")
 CSRC = os.path.join(ROOT, "needletail_amd", "csrc")
 HIP, RULE_HPP, CONSUMER = (os.path.join(CSRC, f) for f in ("ntk_record_minhash.hip", "ntk_rmh_rule.hpp", "ntk_consumer.hpp"))
+# the memory layer of the scaffold (ntk_device_mem.hpp, which ntk_consumer.hpp includes): what it defines, and nobody else does
+MEM = os.path.join(CSRC, "ntk_device_mem.hpp")
+MEM_DEFS = (r"struct DeviceArray\b\s*\{", r"struct Pinned\b\s*\{", r"\bint\s+with_tmp\s*\(")
 BINDING = os.path.join(ROOT, "needletail_amd", "record_minhashing.py")
 EXAMPLE = os.path.join(ROOT, "examples", "sketch_records.cpp")
 GPU_TESTS = "test_gpu_record_minhash.py"
@@ -197,6 +200,13 @@ def test_the_shared_pieces_are_used_and_not_defined_again():
         assert re.search(rf"\b{name}\([^)]*\)\s*\{{", consumer), (name, "not defined in ntk_consumer.hpp")
         for text in (src, rule):
             assert not re.search(rf"\b{name}\([^)]*\)\s*\{{", text), (name, "defined again")
+    assert '#include "ntk_device_mem.hpp"' in consumer
+    # rocPRIM's temporary storage grows with headroom (n + n/2 + 64), as every other array a run sizes: stats reports its bytes
+    assert len(re.findall(r"\bwith_tmp\(", src)) == len(re.findall(r"\bwith_tmp\(m->tmp, st, grow_half_again, ", src)) == 5
+    for pat in MEM_DEFS:
+        assert len(re.findall(pat, open(MEM).read())) == 1, (pat, "not defined in ntk_device_mem.hpp")
+        for text in (src, rule):
+            assert not re.search(pat, text), (pat, "defined again")
     walker = "ntk_wide_" + "walk"
     for path in (HIP, RULE_HPP, HEADER, BINDING, EXAMPLE):
         text = open(path).read()

@@ -22,6 +22,7 @@ HEADER = os.path.join(ROOT, "include", "needletail_amd_sketch.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_sketch.hip")
 CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 WIDE_HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_count.hip")
+WALK_HPP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_walk.hpp")
 GPU_TESTS = "test_gpu_sketch.py"
 
 # every kernel of the sketch library with the test that launches it
@@ -125,8 +126,11 @@ def test_sketch_constants_are_the_models():
     assert int(chunk.group(1)) << int(chunk.group(2)) == S.CHUNK == CM.CHUNK
     assert not re.search(r"kChunkBases\s*=", src), "the chunk length is ntk_chunks.hpp's alone"
     assert int(re.search(r"kSketchThreads = (\d+);", src).group(1)) == S.THREADS
-    # the wide walker restates wt_count_kernel's: the same lane geometry, k range and per-byte rules as ntk_wide_count.hip
-    for text in (src, wide):
+    # the wide walker (ntk_wide_walk.hpp, which the sketch includes) restates wt_count_kernel's: the same lane geometry, k range and
+    # per-byte rules as ntk_wide_count.hip
+    assert '#include "ntk_wide_walk.hpp"' in src
+    walk = open(WALK_HPP).read()
+    for text in (walk, wide):
         assert int(re.search(r"kLaneRun = (\d+);", text).group(1)) == S.LANE_RUN
         assert int(re.search(r"kPrime = (\d+);", text).group(1)) == S.PRIME
         assert re.search(r"kKMax = (\d+);", text).group(1) == "63"
@@ -135,7 +139,7 @@ def test_sketch_constants_are_the_models():
                  "const uint64_t c = ((b >> 1) ^ (b >> 2)) & 3;", "fh = ((fh << 2) | (fl >> 62)) & hi_mask;", "fl = (fl << 2) | c;",
                  "rl = (rl >> 2) | (rh << 62);", "rh = (rh >> 2) | ((3 - c) << rc_shift);", "run = base ? run + 1 : 0;",
                  "const bool fwd = fh < rh || (fh == rh && fl <= rl);"):
-        assert rule in norm(src) and rule in norm(wide), rule
+        assert rule in norm(walk) and rule in norm(wide), rule
 
 
 def _int_rank(h):

@@ -21,6 +21,7 @@ HEADER = os.path.join(ROOT, "include", "needletail_amd_trim.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_trim.hip")
 CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 RUNS_HPP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_trim_runs.hpp")
+MEM = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_device_mem.hpp")   # how the handle owns its arrays
 GPU_TESTS = "test_gpu_trim.py"
 OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so",
               "libneedletail_amd_abundance.so")
@@ -136,12 +137,18 @@ def test_scratch_bound_arithmetic():
     8 B per 16 384 bases + 16 B for the list of long records."""
     import _count_model as CM
     src, hdr = open(HIP).read(), re.sub(r"\s*\n \*\s*", " ", open(HEADER).read())
-    assert re.search(r"ntk_kmer_table_lookup_device\(t->table, t->scratch\.d_values \+ c\.skip\(\), c\.end - c\.start, t->d_counts\)", src)
-    assert re.search(r"grow\(t->d_counts, t->chunk_bases, \(chunk_bases\(n_bytes\) \+ 15\) & ~\(uint64_t\)15, sizeof\(uint64_t\)\)", src)
+    assert re.search(r"ntk_kmer_table_lookup_device\(t->table, t->scratch\.d_values\.p \+ c\.skip\(\), c\.end - c\.start, t->d_counts\.p\)", src)
+    # every array of the handle grows to exactly what is asked for (grow_exact of ntk_device_mem.hpp), in elements of its type
+    assert re.search(r"uint64_t grow_exact\(uint64_t, uint64_t need\) \{ return need; \}", open(MEM).read())
+    assert re.search(r"DeviceArray<uint64_t> d_counts;", src) and re.search(r"DeviceArray<uint64_t> d_solid, d_valid;", src)
+    assert re.search(r"DeviceArray<ScanItem> d_scan;", src) and re.search(r"DeviceArray<uint64_t> d_long;", src)
+    assert re.search(r"t->d_counts\.ensure\(t->stream, \(chunk_bases\(n_bytes\) \+ 15\) & ~\(uint64_t\)15, grow_exact\)", src)
+    for plane in ("d_solid", "d_valid"):
+        assert re.search(rf"t->{plane}\.ensure\(t->stream, planes_words\(n_bytes\), grow_exact\)", src)
     assert re.search(r"uint64_t chunk_bases\(uint64_t n_bytes\) \{ return n_bytes < kChunkBases \? n_bytes : kChunkBases; \}", open(CHUNKS).read())
     assert re.search(r"uint64_t planes_words\(uint64_t n_bytes\) \{ return \(n_bytes \+ 63\) / 64 \+ 1; \}", src)
-    assert re.search(r"grow\(t->d_scan, t->scan_items, n_records \+ 1, sizeof\(ScanItem\)\)", src)
-    assert re.search(r"grow\(t->d_long, t->long_cap, \(n_bytes >> 14\) \+ 2, sizeof\(uint64_t\)\)", src)
+    assert re.search(r"t->d_scan\.ensure\(t->stream, n_records \+ 1, grow_exact\)", src)
+    assert re.search(r"t->d_long\.ensure\(t->stream, \(n_bytes >> 14\) \+ 2, grow_exact\)", src)
     assert re.search(r"struct ScanItem \{\s*uint64_t bytes, records;", src)
     for phrase in ("8 B per base of at most 64 MiB of bases", "no batch-long count array", "1/8 B per base each, plus 16 B",
                    "16 B per record plus 16 B", "8 B per 16 384 bases"):

@@ -190,8 +190,19 @@ def llvm_bin(tool: str) -> str:
     return tool
 
 
+_KERNELS = {}   # (path, mtime, size, arch) -> library_kernels: a run unbundles each file once
+
+
 def library_kernels(so_path: str, arch: str = "gfx950") -> set:
     """The short names of every kernel (its `.kd` symbol) in the library's code objects for `arch`."""
+    st = os.stat(so_path)
+    key = (os.path.abspath(so_path), st.st_mtime_ns, st.st_size, arch)
+    if key not in _KERNELS:
+        _KERNELS[key] = frozenset(_unbundled_kernels(so_path, arch))
+    return set(_KERNELS[key])
+
+
+def _unbundled_kernels(so_path: str, arch: str) -> set:
     with tempfile.TemporaryDirectory() as td:
         fb = os.path.join(td, "fatbin")
         subprocess.check_call([llvm_bin("llvm-objcopy"), f"--dump-section=.hip_fatbin={fb}", so_path, os.path.join(td, "stripped")])

@@ -1,77 +1,42 @@
-"""CPU-side checks of the abundance library (include/needletail_amd_abundance.h, libneedletail_amd_abundance.so): exports, the C header,
-the link to the core and the count library, the kernels it ships (each names the test that launches it), the loud error without a
-device, and the host model (tests/_abundance_model.py) on hand-made counts."""
-import ctypes as C
+"""CPU-side checks of the abundance library (include/needletail_amd_abundance.h, libneedletail_amd_abundance.so) beyond those every library
+is held to (tests/test_consumer_abi.py): the row layout, the constants the GPU tests aim at, the refusal of a wide table, and the host
+model (tests/_abundance_model.py) on hand-made counts."""
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import _abundance_model as A
-import _builds as B
+import _libraries as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "needletail_amd")
-SO = os.path.join(LIBDIR, "libneedletail_amd_abundance.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_abundance.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_abundance.hip")
 CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
-GPU_TESTS = "test_gpu_abundance.py"
-OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so")
 
 A_REG_WINDOWS, A_LONG_RECORD = 192, 65536   # tests/test_gpu_abundance.py REG_WINDOWS, LONG_RECORD
-
-# every kernel of the abundance library with the test that launches it
-ABUNDANCE_KERNELS = {
-    "(anonymous namespace)::ra_wave_kernel((anonymous namespace)::RaArgs)": "test_random_records_match_the_oracle",
-    "(anonymous namespace)::ra_block_kernel((anonymous namespace)::RaArgs)": "test_long_records_on_both_sides_of_the_threshold",
-}
-
-
-def _built():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "needletail_amd", "csrc")])
-    return SO
-
-
-def _header_symbols(path):
-    hdr = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ntk_[a-z0-9_]+)\s*\(", hdr)))
+ROW = L.BY_NAME["abundance"]
 
 
 def test_every_declared_function_is_exported_and_listed():
-    from needletail_amd import abundance
-    lib = C.CDLL(_built())
-    syms = _header_symbols(HEADER)
-    assert syms == ["ntk_read_abundance_create", "ntk_read_abundance_destroy", "ntk_read_abundance_run_device", "ntk_read_abundance_trim"]
-    for s in syms:
-        assert hasattr(lib, s), f"{s} declared in include/needletail_amd_abundance.h but not exported"
-    assert sorted(abundance.SYMBOLS) == syms
-    assert abundance.COLUMNS == A.COLUMNS
-    import needletail_amd as nt
-    assert nt.ReadAbundance is abundance.ReadAbundance and "ReadAbundance" in nt.__all__
+    L.check_exports(ROW)
 
 
-def test_abundance_library_links_the_core_and_the_count_library_by_rpath():
-    out = subprocess.run(["readelf", "-d", _built()], capture_output=True, text=True).stdout
-    needed = re.findall(r"NEEDED.*\[(.*?)\]", out)
-    assert "libneedletail_amd.so" in needed and "libneedletail_amd_count.so" in needed, needed
-    assert "$ORIGIN" in out
-    assert "libneedletail_amd_wide_count.so" not in needed and "libneedletail_amd_sketch.so" not in needed
+def test_header_compiles_as_c(tmp_path):
+    L.check_header(ROW, tmp_path)
 
 
-def test_header_compiles_as_c():
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "t.c")
-        with open(src, "w") as f:
-            f.write('#include "needletail_amd_abundance.h"\nint main(void) { struct ntk_read_abundance_row r; r.median = 48; '
-                    "return sizeof r == r.median ? 0 : 1; }\n")
-        r = subprocess.run(["gcc", "-std=c11", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-c", "-o",
-                            os.path.join(td, "t.o"), src], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+def test_every_kernel_names_the_test_that_launches_it():
+    L.check_kernels(ROW)
+
+
+def test_product_files_never_name_the_checker():
+    L.check_product_files_never_name_the_checker(ROW)
+
+
+def test_no_device_is_a_loud_error():
+    L.check_no_device(ROW)
 
 
 def test_row_layout_is_the_columns():
@@ -79,27 +44,8 @@ def test_row_layout_is_the_columns():
     body = re.search(r"struct ntk_read_abundance_row \{(.*?)\};", hdr, re.S).group(1)
     fields = [f.strip() for decl in re.findall(r"uint64_t ([^;]+);", body) for f in decl.split(",")]
     assert tuple(fields) == A.COLUMNS
-
-
-def test_every_kernel_names_the_test_that_launches_it():
-    names = B.library_kernels(_built())
-    assert names == set(ABUNDANCE_KERNELS), sorted(names ^ set(ABUNDANCE_KERNELS))
-    src = open(os.path.join(ROOT, "tests", GPU_TESTS)).read()
-    for sym, test in ABUNDANCE_KERNELS.items():
-        assert re.search(rf"^def {re.escape(test)}\(", src, re.M), (sym, test)
-
-
-def test_no_abundance_kernel_leaks_into_the_other_libraries():
-    _built()
-    for name in OTHER_LIBS:
-        leaked = {n for n in B.library_kernels(os.path.join(LIBDIR, name)) if re.search(r"(?:^|::)ra_|abundance", n)}
-        assert not leaked, (name, leaked)
-
-
-def test_product_files_never_name_the_checker():
-    for path in (HEADER, HIP, os.path.join(ROOT, "needletail_amd", "abundance.py"), os.path.join(ROOT, "examples", "read_abundance.cpp")):
-        txt = open(path).read()
-        assert not re.search(r"\boracle\b|ntko_", txt), path
+    from needletail_amd import abundance
+    assert abundance.COLUMNS == A.COLUMNS
 
 
 def test_kernel_constants_are_the_tests():
@@ -112,19 +58,6 @@ def test_kernel_constants_are_the_tests():
     assert int(re.search(r"kRegRounds = (\d+);", src).group(1)) * 64 == A_REG_WINDOWS
     assert int(re.search(r"kLongRecord = (\d+);", src).group(1)) == A_LONG_RECORD
     assert not re.search(r"\basm\b|__asm", src), "plain HIP C++"
-
-
-def test_no_device_is_a_loud_error():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    import needletail_amd as nt
-    from needletail_amd import abundance, engine
-    abundance.lib()   # the library itself loads without a device
-    engine._default_ctx = None
-    with pytest.raises(nt.NtkError) as e:
-        nt.ReadAbundance(nt.KmerTable(21, nt.PATH_BITS_CANONICAL, 1000))
-    assert e.value.status == 4   # NTK_ERR_NO_DEVICE
 
 
 def test_wide_table_is_a_type_error():

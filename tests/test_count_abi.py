@@ -1,64 +1,53 @@
-"""CPU-side checks of the count library (include/needletail_amd_count.h, libneedletail_amd_count.so): exports, C headers, the core entry
-it needs, the kernels it ships (each names the test that launches it) and the loud error without a device."""
+"""CPU-side checks of the count library (include/needletail_amd_count.h, libneedletail_amd_count.so) beyond those every library is held to
+(tests/test_consumer_abi.py): the core entry it needs, the shared pieces defined once across all the libraries, who allocates, and the
+host model of the table (tests/_count_model.py) with its constants tied to the kernel source."""
 import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-import _builds as B
 import _count_model as M
+import _libraries as L
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "needletail_amd", "libneedletail_amd_count.so")
-CORE = os.path.join(ROOT, "needletail_amd", "libneedletail_amd.so")
-HEADER = os.path.join(ROOT, "include", "needletail_amd_count.h")
-HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_count.hip")
-WIDE_HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_count.hip")
-CSRC = os.path.join(ROOT, "needletail_amd", "csrc")
+CSRC, CORE = L.CSRC, L.CORE_SO
+HIP = L.BY_NAME["count"].hip
 COMMON = os.path.join(CSRC, "ntk_count_common.hpp")   # what the narrow and the wide table share
 CONSUMER = os.path.join(CSRC, "ntk_consumer.hpp")     # what every library on the core's ABI shares
 CHUNKS = os.path.join(CSRC, "ntk_chunks.hpp")         # the chunk geometry
 # the memory layer of the scaffold (ntk_device_mem.hpp, which ntk_consumer.hpp includes): what it defines, and nobody else does
 MEM = os.path.join(CSRC, "ntk_device_mem.hpp")
 MEM_DEFS = (r"struct DeviceArray\b\s*\{", r"struct Pinned\b\s*\{", r"\bint\s+with_tmp\s*\(")
-# the six library sources
-SOURCES = [os.path.join(CSRC, f"ntk_{name}.hip") for name in ("count", "wide_count", "sketch", "abundance", "trim", "minhash")]
-
-# every kernel of the count library with the test that launches it (file, test function); rocPRIM's sort kernels by namespace
-COUNT_KERNELS = {
-    "(anonymous namespace)::kt_insert_kernel((anonymous namespace)::InsertArgs)": ("test_gpu_count.py", "test_random_records_match_the_oracle"),
-    "(anonymous namespace)::ct_extract_count_kernel": ("test_gpu_count.py", "test_random_records_match_the_oracle"),
-    "(anonymous namespace)::ct_extract_scan_kernel": ("test_gpu_count.py", "test_random_records_match_the_oracle"),
-    "(anonymous namespace)::kt_extract_scatter_kernel": ("test_gpu_count.py", "test_random_records_match_the_oracle"),
-    "(anonymous namespace)::ct_spectrum_kernel": ("test_gpu_count.py", "test_genome_sampled_reads_spectrum"),
-    "(anonymous namespace)::kt_lookup_kernel": ("test_gpu_count.py", "test_golden_28s_and_prjna271013"),
-}
-SORT_NAMESPACE = "rocprim::"
-
-
-def _built():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "needletail_amd", "csrc")])
-    return SO
-
-
-def _header_symbols(path):
-    hdr = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ntk_[a-z0-9_]+)\s*\(", hdr)))
+ROW = L.BY_NAME["count"]
 
 
 def test_every_declared_function_is_exported_and_listed():
-    from needletail_amd import counting
-    lib = C.CDLL(_built())
-    syms = _header_symbols(HEADER)
-    assert len(syms) == 8
-    for s in syms:
-        assert hasattr(lib, s), f"{s} declared in include/needletail_amd_count.h but not exported"
-    assert sorted(counting.SYMBOLS) == syms
+    L.check_exports(ROW)
+
+
+@pytest.mark.parametrize("header", ["needletail_amd.h", "needletail_amd_count.h"])
+def test_headers_compile_as_c(header, tmp_path):
+    src = tmp_path / "t.c"
+    src.write_text(f'#include "{header}"\nint main(void) {{ return 0; }}\n')
+    r = subprocess.run(["gcc", "-std=c11", "-pedantic", "-Wall", "-Werror", "-I" + L.INCLUDE, "-c", "-o", str(tmp_path / "t.o"), str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    if header == os.path.basename(ROW.header):
+        L.check_header(ROW, tmp_path)
+
+
+def test_every_kernel_names_the_test_that_launches_it():
+    L.check_kernels(ROW)
+
+
+def test_product_files_never_name_the_checker():
+    L.check_product_files_never_name_the_checker(ROW)
+
+
+def test_no_device_is_a_loud_error():
+    L.check_no_device(ROW)
 
 
 def test_core_exports_ctx_stream():
@@ -70,41 +59,9 @@ def test_core_exports_ctx_stream():
     assert lib.ntk_ctx_stream(None, C.byref(dev), C.byref(stream)) == 2   # NTK_ERR_BAD_ARG
 
 
-def test_count_library_links_the_core_by_rpath():
-    out = subprocess.run(["readelf", "-d", _built()], capture_output=True, text=True).stdout
-    assert "libneedletail_amd.so" in out and "$ORIGIN" in out
-
-
-@pytest.mark.parametrize("header", ["needletail_amd.h", "needletail_amd_count.h"])
-def test_headers_compile_as_c(header):
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "t.c")
-        with open(src, "w") as f:
-            f.write(f'#include "{header}"\nint main(void) {{ return 0; }}\n')
-        r = subprocess.run(["gcc", "-std=c11", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-c", "-o",
-                            os.path.join(td, "t.o"), src], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-
-
-def test_every_kernel_names_the_test_that_launches_it():
-    names = B.library_kernels(_built())
-    ours = {n for n in names if not n.startswith(SORT_NAMESPACE)}
-    assert ours == set(COUNT_KERNELS), sorted(ours ^ set(COUNT_KERNELS))
-    assert any("radix" in n for n in names - ours)   # the extract's sort
-    for sym, (fname, test) in COUNT_KERNELS.items():
-        src = open(os.path.join(ROOT, "tests", fname)).read()
-        assert re.search(rf"^def {re.escape(test)}\(", src, re.M), (sym, fname, test)
-
-
-def test_product_files_never_name_the_checker():
-    for path in (HEADER, HIP, COMMON, CONSUMER, CHUNKS, os.path.join(ROOT, "needletail_amd", "counting.py"), os.path.join(ROOT, "examples", "count_kmers.cpp")):
-        txt = open(path).read()
-        assert not re.search(r"\boracle\b|ntko_", txt), path
-
-
 def test_the_shared_pieces_are_defined_once():
     """The hash, the reductions, the host helpers, the record rule and the chunk walk live in ntk_consumer.hpp only, the extract count /
-    scan and spectrum kernels in ntk_count_common.hpp only: none of the six library sources defines its own copy again."""
+    scan and spectrum kernels in ntk_count_common.hpp only: no library source defines its own copy again."""
     shared = ("fmix64", "wave_sum", "add_agent", "block_sum_u32", "grid_for", "alloc_status", "record_span", "uniform", "for_each_chunk")
     kernel = r"__global__[^{;]*?\bvoid\s+\w*(?:extract_count|extract_scan|spectrum)_kernel\s*\("
     common, consumer = open(COMMON).read(), open(CONSUMER).read()
@@ -117,16 +74,16 @@ def test_the_shared_pieces_are_defined_once():
     for pat in MEM_DEFS:
         assert len(re.findall(pat, mem)) == 1 and not re.search(pat, consumer) and not re.search(pat, common), pat
     assert len(re.findall(kernel, common)) == 3 and not re.search(kernel, consumer)
-    for path in SOURCES:
-        src = open(path).read()
+    for row in L.LIBRARIES:
+        path, src = row.hip, open(row.hip).read()
         for name in shared:
             assert not re.search(rf"\b{name}\([^)]*\)\s*\{{", src), (name, "defined again in", path)
         assert not re.search(kernel, src), ("an extract count / scan or spectrum kernel defined again in", path)
         assert not re.search(r"struct MaterialiseScratch\b", src), path
         for pat in MEM_DEFS:
             assert not re.search(pat, src), (pat, "defined again in", path)
-        # the two tables take the shared pieces through their own header, the other four directly
-        want = "ntk_count_common.hpp" if path in (HIP, WIDE_HIP) else "ntk_consumer.hpp"
+        # the two tables take the shared pieces through their own header, the others directly
+        want = "ntk_count_common.hpp" if row.name in ("count", "wide_count") else "ntk_consumer.hpp"
         assert f'#include "{want}"' in src, path
 
 
@@ -140,18 +97,6 @@ def test_only_the_memory_layer_and_the_core_allocate():
             found.add(name)
     assert "ntk_device_mem.hpp" in found
     assert [f for f in found if f != "ntk_device_mem.hpp" and not core.search(f)] == []
-
-
-def test_no_device_is_a_loud_error():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    import needletail_amd as nt
-    from needletail_amd import engine
-    engine._default_ctx = None
-    with pytest.raises(nt.NtkError) as e:
-        nt.KmerTable(21, nt.PATH_BITS_CANONICAL, 1000)
-    assert e.value.status == 4   # NTK_ERR_NO_DEVICE
 
 
 # ---- the host model of the table (tests/_count_model.py), which the edge tests aim with --------------------------------------

@@ -1,23 +1,20 @@
-"""CPU-side checks of the MinHash library (include/needletail_amd_minhash.h, libneedletail_amd_minhash.so): exports, the C header, the
-link to the core, the kernels it ships (each names the test that launches it), the loud error without a device, the constants and the
-byte walker tied to the sketch's and the wide table's sources, the host model's (tests/_minhash_model.py) algebra, and
-ntk_minhash_compare - host code - against the model's set restatement."""
+"""CPU-side checks of the MinHash library (include/needletail_amd_minhash.h, libneedletail_amd_minhash.so) beyond those every library is
+held to (tests/test_consumer_abi.py): the struct fields of the bindings, the constants and the byte walker tied to the sketch's and the
+wide table's sources, the host model's (tests/_minhash_model.py) algebra, and ntk_minhash_compare - host code - against the model's set
+restatement."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import _builds as B
 import _count_model as CM
+import _libraries as L
 import _minhash_model as M
 import _sketch_model as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "needletail_amd")
-SO = os.path.join(LIBDIR, "libneedletail_amd_minhash.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_minhash.h")
 SKETCH_HEADER = os.path.join(ROOT, "include", "needletail_amd_sketch.h")
 CSRC = os.path.join(ROOT, "needletail_amd", "csrc")
@@ -25,58 +22,28 @@ HIP, WALK_HPP = os.path.join(CSRC, "ntk_minhash.hip"), os.path.join(CSRC, "ntk_w
 CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 SKETCH_HIP, WIDE_HIP = os.path.join(CSRC, "ntk_sketch.hip"), os.path.join(CSRC, "ntk_wide_count.hip")
 GPU_TESTS = "test_gpu_minhash.py"
-OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so",
-              "libneedletail_amd_abundance.so", "libneedletail_amd_trim.so")
-PRIM_NAMESPACE = "rocprim::"
 ERR_BAD_ARG = 2
+ROW = L.BY_NAME["minhash"]
 
-# every kernel of the MinHash library with the test that launches it
-MINHASH_KERNELS = {
-    "(anonymous namespace)::mh_filter_kernel((anonymous namespace)::FilterArgs)": "test_random_records_match_the_model",
-    "(anonymous namespace)::mh_wide_filter_kernel((anonymous namespace)::WideFilterArgs)": "test_random_records_match_the_model_wide",
-}
-
-
-def _built():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-s", "-C", CSRC])
-    return SO
-
-
-def _header_symbols(path):
-    hdr = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ntk_[a-z0-9_]+)\s*\(", hdr)))
-
-
-# ---- the library and the build ------------------------------------------------------------------------------------------------------
 
 def test_every_declared_function_is_exported_and_listed():
-    from needletail_amd import minhashing
-    lib = C.CDLL(_built())
-    syms = _header_symbols(HEADER)
-    assert syms == sorted("ntk_minhash_" + c for c in ("create", "destroy", "reset", "add_device", "stats", "read", "merge", "compare"))
-    assert len(syms) == 8
-    for s in syms:
-        assert hasattr(lib, s), f"{s} declared in include/needletail_amd_minhash.h but not exported"
-    assert sorted(minhashing.SYMBOLS) == syms
-    import needletail_amd as nt
-    assert nt.KmerMinHash is minhashing.KmerMinHash and "KmerMinHash" in nt.__all__
+    L.check_exports(ROW)
 
 
 def test_header_compiles_as_c(tmp_path):
-    src = tmp_path / "t.c"
-    src.write_text('#include "needletail_amd_minhash.h"\nint main(void) { struct ntk_minhash_stats s; struct ntk_minhash_comparison c; '
-                   "s.num = NTK_MINHASH_MAX_NUM; c.dot = 0.0; "
-                   "return s.num == 1048576 && c.dot == 0.0 && sizeof s == 72 && sizeof c == 56 && NTK_MINHASH_XOR != 0 && "
-                   "NTK_MINHASH_BUFFER_DEFAULT == 4194304 && NTK_MINHASH_BUFFER_MIN == 64 && NTK_MINHASH_BUFFER_MAX == 268435456 ? 0 : 1; }\n")
-    exe = tmp_path / "t"
-    r = subprocess.run(["gcc", "-std=c11", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert subprocess.run([str(exe)]).returncode == 0
-    from needletail_amd import minhashing as K
-    assert C.sizeof(K.Stats) == 72 and C.sizeof(K.Comparison) == 56
-    assert (K.MAX_NUM, K.BUFFER_DEFAULT, K.BUFFER_MIN, K.BUFFER_MAX) == (M.MAX_NUM, M.BUFFER_DEFAULT, M.BUFFER_MIN, M.BUFFER_MAX)
+    L.check_header(ROW, tmp_path)
+
+
+def test_every_kernel_names_the_test_that_launches_it():
+    L.check_kernels(ROW)
+
+
+def test_product_files_never_name_the_checker():
+    L.check_product_files_never_name_the_checker(ROW)
+
+
+def test_no_device_is_a_loud_error():
+    L.check_no_device(ROW)
 
 
 def test_struct_fields_are_the_bindings():
@@ -86,51 +53,8 @@ def test_struct_fields_are_the_bindings():
         body = re.search(rf"struct {tag} \{{(.*?)\}};", hdr, re.S).group(1)
         fields = [f.strip() for decl in re.findall(r"(?:uint64_t|uint32_t|double) ([^;]+);", body) for f in decl.split(",")]
         assert fields == [name for name, _ in cls._fields_], tag
-
-
-def test_minhash_library_links_the_core_by_rpath_and_no_count_library():
-    out = subprocess.run(["readelf", "-d", _built()], capture_output=True, text=True).stdout
-    needed = re.findall(r"NEEDED.*\[(.*?)\]", out)
-    assert "libneedletail_amd.so" in needed and "$ORIGIN" in out
-    assert [n for n in needed if n.startswith("libneedletail_amd")] == ["libneedletail_amd.so"], needed
-
-
-def test_every_kernel_names_the_test_that_launches_it():
-    names = B.library_kernels(_built())
-    ours = {n for n in names if not n.startswith(PRIM_NAMESPACE)}
-    assert ours == set(MINHASH_KERNELS), sorted(ours ^ set(MINHASH_KERNELS))
-    assert all(re.search(r"::mh_[a-z_]+kernel\(", n) for n in ours)
-    prim = names - ours   # the merge step's sort, run-length encoding, merge and reduction
-    assert any("sort" in n for n in prim) and any("merge" in n for n in prim) and any("reduce_by_key" in n for n in prim)
-    src = open(os.path.join(ROOT, "tests", GPU_TESTS)).read()
-    for sym, test in MINHASH_KERNELS.items():
-        assert re.search(rf"^def {re.escape(test)}\(", src, re.M), (sym, test)
-
-
-def test_no_minhash_kernel_leaks_into_the_other_libraries():
-    _built()
-    for name in OTHER_LIBS:
-        leaked = {n for n in B.library_kernels(os.path.join(LIBDIR, name)) if re.search(r"(?:^|::)mh_|minhash", n)}
-        assert not leaked, (name, leaked)
-
-
-def test_product_files_never_name_the_checker():
-    for path in (HEADER, HIP, WALK_HPP, os.path.join(ROOT, "needletail_amd", "minhashing.py"),
-                 os.path.join(ROOT, "examples", "minhash_sketch.cpp"), os.path.join(ROOT, "tools", "minhash_bench.py")):
-        txt = open(path).read()
-        assert not re.search(r"\boracle\b|ntko_", txt), path
-
-
-def test_no_device_is_a_loud_error():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    import needletail_amd as nt
-    from needletail_amd import engine
-    engine._default_ctx = None
-    with pytest.raises(nt.NtkError) as e:
-        nt.KmerMinHash(21, nt.PATH_BITS_CANONICAL, num=1000)
-    assert e.value.status == 4   # NTK_ERR_NO_DEVICE
+    assert C.sizeof(K.Stats) == 72 and C.sizeof(K.Comparison) == 56   # the header's, which its C program states (tests/_libraries.py)
+    assert (K.MAX_NUM, K.BUFFER_DEFAULT, K.BUFFER_MIN, K.BUFFER_MAX) == (M.MAX_NUM, M.BUFFER_DEFAULT, M.BUFFER_MIN, M.BUFFER_MAX)
 
 
 # ---- constants, the hash and the walker --------------------------------------------------------------------------------------------

@@ -1,106 +1,44 @@
-"""CPU-side checks of the sketch library (include/needletail_amd_sketch.h, libneedletail_amd_sketch.so): exports, the C header, the link
-to the core, the kernels it ships (each names the test that launches it), the loud error without a device, the host model
-(tests/_sketch_model.py) with its constants tied to the kernel source, and the capacity rule's accuracy sweep."""
-import ctypes as C
+"""CPU-side checks of the sketch library (include/needletail_amd_sketch.h, libneedletail_amd_sketch.so) beyond those every library is held
+to (tests/test_consumer_abi.py): the host model (tests/_sketch_model.py) with its constants tied to the kernel source, and the capacity
+rule's accuracy sweep."""
 import math
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-import _builds as B
 import _count_model as CM
+import _libraries as L
 import _sketch_model as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "needletail_amd")
-SO = os.path.join(LIBDIR, "libneedletail_amd_sketch.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_sketch.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_sketch.hip")
 CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 WIDE_HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_count.hip")
 WALK_HPP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_walk.hpp")
-GPU_TESTS = "test_gpu_sketch.py"
-
-# every kernel of the sketch library with the test that launches it
-SKETCH_KERNELS = {
-    "(anonymous namespace)::sk_update_kernel((anonymous namespace)::UpdateArgs)": "test_random_records_match_the_model",
-    "(anonymous namespace)::sk_wide_update_kernel((anonymous namespace)::WideArgs)": "test_random_records_match_the_model_wide",
-}
-
-
-def _built():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "needletail_amd", "csrc")])
-    return SO
-
-
-def _header_symbols(path):
-    hdr = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ntk_[a-z0-9_]+)\s*\(", hdr)))
+ROW = L.BY_NAME["sketch"]
 
 
 def test_every_declared_function_is_exported_and_listed():
-    from needletail_amd import sketching
-    lib = C.CDLL(_built())
-    syms = _header_symbols(HEADER)
-    assert len(syms) == 7
-    for s in syms:
-        assert hasattr(lib, s), f"{s} declared in include/needletail_amd_sketch.h but not exported"
-    assert sorted(sketching.SYMBOLS) == syms
-    import needletail_amd as nt
-    assert nt.KmerSketch is sketching.KmerSketch
+    L.check_exports(ROW)
 
 
-def test_sketch_library_links_the_core_by_rpath():
-    out = subprocess.run(["readelf", "-d", _built()], capture_output=True, text=True).stdout
-    assert "libneedletail_amd.so" in out and "$ORIGIN" in out
-
-
-def test_header_compiles_as_c():
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "t.c")
-        with open(src, "w") as f:
-            f.write('#include "needletail_amd_sketch.h"\nint main(void) { struct ntk_kmer_sketch_estimate e; e.capacity = NTK_SKETCH_REGISTERS; '
-                    "return e.capacity == 16384 && NTK_SKETCH_XOR != 0 ? 0 : 1; }\n")
-        r = subprocess.run(["gcc", "-std=c11", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-c", "-o",
-                            os.path.join(td, "t.o"), src], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+def test_header_compiles_as_c(tmp_path):
+    L.check_header(ROW, tmp_path)
 
 
 def test_every_kernel_names_the_test_that_launches_it():
-    names = B.library_kernels(_built())
-    assert names == set(SKETCH_KERNELS), sorted(names ^ set(SKETCH_KERNELS))
-    src = open(os.path.join(ROOT, "tests", GPU_TESTS)).read()
-    for sym, test in SKETCH_KERNELS.items():
-        assert re.search(rf"^def {re.escape(test)}\(", src, re.M), (sym, test)
-
-
-def test_no_sketch_kernel_leaks_into_the_other_libraries():
-    for name in ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so"):
-        leaked = {n for n in B.library_kernels(os.path.join(LIBDIR, name)) if re.search(r"(?:^|::)sk_|sketch", n)}
-        assert not leaked, (name, leaked)
+    L.check_kernels(ROW)
 
 
 def test_product_files_never_name_the_checker():
-    for path in (HEADER, HIP, os.path.join(ROOT, "needletail_amd", "sketching.py"), os.path.join(ROOT, "examples", "count_kmers.cpp")):
-        txt = open(path).read()
-        assert not re.search(r"\boracle\b|ntko_", txt), path
+    L.check_product_files_never_name_the_checker(ROW)
 
 
 def test_no_device_is_a_loud_error():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    import needletail_amd as nt
-    from needletail_amd import engine
-    engine._default_ctx = None
-    with pytest.raises(nt.NtkError) as e:
-        nt.KmerSketch(21, nt.PATH_BITS_CANONICAL)
-    assert e.value.status == 4   # NTK_ERR_NO_DEVICE
+    L.check_no_device(ROW)
 
 
 # ---- the host model (tests/_sketch_model.py), which the GPU tests hold the registers to ----------------------------------------------

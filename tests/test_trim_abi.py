@@ -1,8 +1,8 @@
-"""CPU-side checks of the trim library (include/needletail_amd_trim.h, libneedletail_amd_trim.so): exports, the C header, the link to the
-core and the count library, the kernels it ships (each names the test that launches it), the scratch bound's arithmetic, the loud error
-without a device, the host model (tests/_trim_model.py) on hand-made solid patterns, and the run search of csrc/ntk_trim_runs.hpp,
-compiled here with g++, against that model: exhaustively on short bit strings at every bit offset, on random strings around the word
-and round seams, and split at every point into two parts that are combined."""
+"""CPU-side checks of the trim library (include/needletail_amd_trim.h, libneedletail_amd_trim.so) beyond those every library is held to
+(tests/test_consumer_abi.py): the row layout and the modes, the scratch bound's arithmetic, the refusal of a wide table, the host model
+(tests/_trim_model.py) on hand-made solid patterns, and the run search of csrc/ntk_trim_runs.hpp, compiled here with g++, against that
+model: exhaustively on short bit strings at every bit offset, on random strings around the word and round seams, and split at every point
+into two parts that are combined."""
 import ctypes as C
 import os
 import re
@@ -11,79 +11,38 @@ import subprocess
 import numpy as np
 import pytest
 
-import _builds as B
+import _libraries as L
 import _trim_model as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "needletail_amd")
-SO = os.path.join(LIBDIR, "libneedletail_amd_trim.so")
 HEADER = os.path.join(ROOT, "include", "needletail_amd_trim.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_trim.hip")
 CHUNKS = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_chunks.hpp")   # the chunk geometry every library walks
 RUNS_HPP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_trim_runs.hpp")
 MEM = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_device_mem.hpp")   # how the handle owns its arrays
-GPU_TESTS = "test_gpu_trim.py"
-OTHER_LIBS = ("libneedletail_amd.so", "libneedletail_amd_count.so", "libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so",
-              "libneedletail_amd_abundance.so")
-SCAN_NAMESPACE = "rocprim::"
 
 T_GROUP_WORDS, T_LONG_PIECES = 32, 2048   # tests/test_gpu_trim.py GROUP_WORDS, LONG_PIECES
-
-# every kernel of the trim library with the test that launches it
-TRIM_KERNELS = {
-    "(anonymous namespace)::rt_solid_kernel((anonymous namespace)::SolidArgs)": "test_random_records_match_the_model",
-    "(anonymous namespace)::rt_interval_kernel((anonymous namespace)::IntervalArgs)": "test_random_records_match_the_model",
-    "(anonymous namespace)::rt_copy_kernel((anonymous namespace)::CopyArgs)": "test_compaction_matches_the_model",
-    "(anonymous namespace)::rt_copy_long_kernel((anonymous namespace)::CopyArgs)": "test_one_record_of_four_million_bases",
-}
-
-
-def _built():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "needletail_amd", "csrc")])
-    return SO
-
-
-def _header_symbols(path):
-    hdr = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ntk_[a-z0-9_]+)\s*\(", hdr)))
+ROW = L.BY_NAME["trim"]
 
 
 def test_every_declared_function_is_exported_and_listed():
-    from needletail_amd import trimming
-    lib = C.CDLL(_built())
-    syms = _header_symbols(HEADER)
-    assert syms == ["ntk_read_trim_compact_device", "ntk_read_trim_create", "ntk_read_trim_destroy", "ntk_read_trim_release",
-                    "ntk_read_trim_run_device"]
-    for s in syms:
-        assert hasattr(lib, s), f"{s} declared in include/needletail_amd_trim.h but not exported"
-    assert sorted(trimming.SYMBOLS) == syms
-    assert trimming.COLUMNS == T.COLUMNS
-    assert (trimming.TRIM_PREFIX, trimming.TRIM_LONGEST) == (T.PREFIX, T.LONGEST)
-    hdr = open(HEADER).read()
-    assert re.search(r"NTK_TRIM_PREFIX = 0,", hdr) and re.search(r"NTK_TRIM_LONGEST = 1\b", hdr)
-    import needletail_amd as nt
-    assert nt.ReadTrimmer is trimming.ReadTrimmer and "ReadTrimmer" in nt.__all__
-
-
-def test_trim_library_links_the_core_and_the_count_library_by_rpath():
-    out = subprocess.run(["readelf", "-d", _built()], capture_output=True, text=True).stdout
-    needed = re.findall(r"NEEDED.*\[(.*?)\]", out)
-    assert "libneedletail_amd.so" in needed and "libneedletail_amd_count.so" in needed, needed
-    assert "$ORIGIN" in out
-    for other in ("libneedletail_amd_wide_count.so", "libneedletail_amd_sketch.so", "libneedletail_amd_abundance.so"):
-        assert other not in needed
+    L.check_exports(ROW)
 
 
 def test_header_compiles_as_c(tmp_path):
-    src = tmp_path / "t.c"
-    src.write_text('#include "needletail_amd_trim.h"\nint main(void) { struct ntk_read_trim_row r; r.length = 32; '
-                   "return sizeof r == r.length && NTK_TRIM_LONGEST == 1 ? 0 : 1; }\n")
-    exe = tmp_path / "t"
-    r = subprocess.run(["gcc", "-std=c11", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-o", str(exe), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert subprocess.run([str(exe)]).returncode == 0   # sizeof(row) == 32
+    L.check_header(ROW, tmp_path)
+
+
+def test_every_kernel_names_the_test_that_launches_it():
+    L.check_kernels(ROW)
+
+
+def test_product_files_never_name_the_checker():
+    L.check_product_files_never_name_the_checker(ROW)
+
+
+def test_no_device_is_a_loud_error():
+    L.check_no_device(ROW)
 
 
 def test_row_layout_is_the_columns():
@@ -91,30 +50,11 @@ def test_row_layout_is_the_columns():
     body = re.search(r"struct ntk_read_trim_row \{(.*?)\};", hdr, re.S).group(1)
     fields = [f.strip() for decl in re.findall(r"uint64_t ([^;]+);", body) for f in decl.split(",")]
     assert tuple(fields) == T.COLUMNS
-
-
-def test_every_kernel_names_the_test_that_launches_it():
-    names = B.library_kernels(_built())
-    ours = {n for n in names if not n.startswith(SCAN_NAMESPACE)}
-    assert ours == set(TRIM_KERNELS), sorted(ours ^ set(TRIM_KERNELS))
-    assert all(re.search(r"::rt_[a-z_]+kernel\(", n) for n in ours)
-    assert any("scan" in n for n in names - ours)   # the compaction's scan
-    src = open(os.path.join(ROOT, "tests", GPU_TESTS)).read()
-    for sym, test in TRIM_KERNELS.items():
-        assert re.search(rf"^def {re.escape(test)}\(", src, re.M), (sym, test)
-
-
-def test_no_trim_kernel_leaks_into_the_other_libraries():
-    _built()
-    for name in OTHER_LIBS:
-        leaked = {n for n in B.library_kernels(os.path.join(LIBDIR, name)) if re.search(r"(?:^|::)rt_|read_trim", n)}
-        assert not leaked, (name, leaked)
-
-
-def test_product_files_never_name_the_checker():
-    for path in (HEADER, HIP, RUNS_HPP, os.path.join(ROOT, "needletail_amd", "trimming.py"), os.path.join(ROOT, "examples", "trim_reads.cpp")):
-        txt = open(path).read()
-        assert not re.search(r"\boracle\b|ntko_", txt), path
+    from needletail_amd import trimming
+    assert trimming.COLUMNS == T.COLUMNS
+    assert (trimming.TRIM_PREFIX, trimming.TRIM_LONGEST) == (T.PREFIX, T.LONGEST)
+    hdr = open(HEADER).read()
+    assert re.search(r"NTK_TRIM_PREFIX = 0,", hdr) and re.search(r"NTK_TRIM_LONGEST = 1\b", hdr)
 
 
 def test_kernel_constants_are_the_tests():
@@ -162,19 +102,6 @@ def test_scratch_bound_arithmetic():
             assert 16 * (n_records + 1) == 16 * n_records + 16
     # a long record of the copy needs more than (kLongPieces - 2) * 16 bytes, so the list's capacity holds every one of them
     assert (T_LONG_PIECES - 2) * 16 >= 16384
-
-
-def test_no_device_is_a_loud_error():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    import needletail_amd as nt
-    from needletail_amd import engine, trimming
-    trimming.lib()   # the library itself loads without a device
-    engine._default_ctx = None
-    with pytest.raises(nt.NtkError) as e:
-        nt.ReadTrimmer(nt.KmerTable(21, nt.PATH_BITS_CANONICAL, 1000))
-    assert e.value.status == 4   # NTK_ERR_NO_DEVICE
 
 
 def test_wide_table_is_a_type_error():

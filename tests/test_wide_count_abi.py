@@ -1,103 +1,41 @@
-"""CPU-side checks of the wide count library (include/needletail_amd_wide_count.h, libneedletail_amd_wide_count.so, k = 33..63):
-exports, the C header, the link to the core, the kernels it ships (each names the test that launches it), the loud error without a
-device, and the host model of the table (tests/_wide_count_model.py) with its constants tied to the kernel source."""
-import ctypes as C
+"""CPU-side checks of the wide count library (include/needletail_amd_wide_count.h, libneedletail_amd_wide_count.so, k = 33..63) beyond
+those every library is held to (tests/test_consumer_abi.py): the host model of the table (tests/_wide_count_model.py) with its constants
+tied to the kernel source."""
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-import _builds as B
 import _count_model as CM
+import _libraries as L
 import _wide_count_model as W
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "needletail_amd", "libneedletail_amd_wide_count.so")
-HEADER = os.path.join(ROOT, "include", "needletail_amd_wide_count.h")
 HIP = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_wide_count.hip")
 COMMON = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_count_common.hpp")   # what the narrow and the wide table share
 CONSUMER = os.path.join(ROOT, "needletail_amd", "csrc", "ntk_consumer.hpp")    # what every library on the core's ABI shares
-GPU_TESTS = "test_gpu_wide_count.py"
-
-# every kernel of the wide count library with the test that launches it; rocPRIM's sort kernels by namespace
-WIDE_KERNELS = {
-    "(anonymous namespace)::wt_count_kernel((anonymous namespace)::CountArgs)": "test_random_records_match_the_oracle",
-    "(anonymous namespace)::ct_extract_count_kernel": "test_random_records_match_the_oracle",
-    "(anonymous namespace)::ct_extract_scan_kernel": "test_random_records_match_the_oracle",
-    "(anonymous namespace)::wt_extract_scatter_kernel(unsigned long const*, unsigned long const*, unsigned long const*, unsigned long, "
-    "unsigned long, unsigned long const*, (anonymous namespace)::WideKey*, unsigned long*)": "test_random_records_match_the_oracle",
-    "(anonymous namespace)::ct_spectrum_kernel": "test_synthetic_reads_agree_with_the_reduce_face",
-    "(anonymous namespace)::wt_lookup_kernel((anonymous namespace)::Table, unsigned int, unsigned long const*, unsigned long, "
-    "unsigned long*)": "test_random_records_match_the_oracle",
-}
-SORT_NAMESPACE = "rocprim::"
-
-
-def _built():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "needletail_amd", "csrc")])
-    return SO
-
-
-def _header_symbols(path):
-    hdr = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ntk_[a-z0-9_]+)\s*\(", hdr)))
+ROW = L.BY_NAME["wide_count"]
 
 
 def test_every_declared_function_is_exported_and_listed():
-    from needletail_amd import wide_counting
-    lib = C.CDLL(_built())
-    syms = _header_symbols(HEADER)
-    assert len(syms) == 8
-    for s in syms:
-        assert hasattr(lib, s), f"{s} declared in include/needletail_amd_wide_count.h but not exported"
-    assert sorted(wide_counting.SYMBOLS) == syms
+    L.check_exports(ROW)
 
 
-def test_wide_count_library_links_the_core_by_rpath():
-    out = subprocess.run(["readelf", "-d", _built()], capture_output=True, text=True).stdout
-    assert "libneedletail_amd.so" in out and "$ORIGIN" in out
-
-
-def test_header_compiles_as_c():
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "t.c")
-        with open(src, "w") as f:
-            f.write('#include "needletail_amd_wide_count.h"\nint main(void) { struct ntk_kmer_table_stats s; (void)s; return 0; }\n')
-        r = subprocess.run(["gcc", "-std=c11", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-c", "-o",
-                            os.path.join(td, "t.o"), src], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+def test_header_compiles_as_c(tmp_path):
+    L.check_header(ROW, tmp_path)
 
 
 def test_every_kernel_names_the_test_that_launches_it():
-    names = B.library_kernels(_built())
-    ours = {n for n in names if not n.startswith(SORT_NAMESPACE)}
-    assert ours == set(WIDE_KERNELS), sorted(ours ^ set(WIDE_KERNELS))
-    assert any("radix" in n for n in names - ours)   # the extract's sort
-    src = open(os.path.join(ROOT, "tests", GPU_TESTS)).read()
-    for sym, test in WIDE_KERNELS.items():
-        assert re.search(rf"^def {re.escape(test)}\(", src, re.M), (sym, test)
+    L.check_kernels(ROW)
 
 
 def test_product_files_never_name_the_checker():
-    for path in (HEADER, HIP, COMMON, CONSUMER, os.path.join(ROOT, "needletail_amd", "wide_counting.py")):
-        txt = open(path).read()
-        assert not re.search(r"\boracle\b|ntko_", txt), path
+    L.check_product_files_never_name_the_checker(ROW)
 
 
 def test_no_device_is_a_loud_error():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    import needletail_amd as nt
-    from needletail_amd import engine
-    engine._default_ctx = None
-    with pytest.raises(nt.NtkError) as e:
-        nt.WideKmerTable(51, nt.PATH_BYTES_CANONICAL, 1000)
-    assert e.value.status == 4   # NTK_ERR_NO_DEVICE
+    L.check_no_device(ROW)
 
 
 # ---- the host model (tests/_wide_count_model.py), which the GPU tests aim with ------------------------------------------------------

@@ -1,41 +1,71 @@
-"""A seeded, structured, differential fuzz of the six k-mer libraries (count table, wide count table, HyperLogLog sketch, read
-abundance, read trimmer with its batch writer, MinHash) against the host models the suite already has.  Shared by
-tests/test_lib_fuzz_inputs.py (CPU: the slices are not vacuous), tests/test_gpu_lib_fuzz.py (the fixed slices) and tools/lib_fuzz.py
-(time-budgeted runs, replay, dump).  Importable without a GPU: torch is imported only inside the device functions.
+"""A seeded, structured, differential fuzz of the eleven k-mer libraries (count table, wide count table, HyperLogLog sketch, read
+abundance, read trimmer with its batch writer, MinHash; per-record MinHash, the sketch set, k-mer set algebra narrow and wide, the de
+Bruijn graph, the coloured index) against the host models the suite already has.  Shared by tests/test_lib_fuzz_inputs.py (CPU: the
+slices are not vacuous), tests/test_gpu_lib_fuzz.py (the fixed slices) and tools/lib_fuzz.py (time-budgeted runs, replay, dump).
+Importable without a GPU: torch is imported only inside the device functions.
 
 Truth is the existing models only: `_count_helpers.oracle_values` / `oracle_items`, `test_gpu_wide_count.oracle_items`,
-`_sketch_model`, `_minhash_model`, `_abundance_model`, `_trim_model`.  Every comparison is `array_equal` / `==`.
+`_sketch_model`, `_minhash_model`, `_abundance_model`, `_trim_model`, `_record_minhash_model`, `_mhset_model`, `_kmer_sets_model`,
+`_dbg_model`, `_colors_model`.  Every comparison is `array_equal` / `==`, the double columns of MinHashSet.compare included (as
+tests/test_gpu_minhash_set.py compares them: the counts are small, every sum is exact in a double).
 
 The generator (`make_case`).  Query records and a related reference set (the table's batch) are sampled from one random genome of a
 few kb with substitution errors, at different and uneven coverage, plus foreign reads and exact duplicates, so that abundances
 differ along a record.  Record content kinds are those of tools/gpu_fuzz.py's make_input (KINDS); record lengths come from EDGE
-lengths derived from the kernels' constants (`edge_lengths`).
+lengths derived from the kernels' constants (`edge_lengths(k, stage)`: the six first stages share one dict, `colors` and
+`record_minhash` add their own).  The six first stages draw exactly what they drew before the newer five were added
+(tests/test_lib_fuzz_inputs.py pins a digest of each slice).
+
+The five newer stages.  `record_minhash`: per-record sketches of the batch, of a prefix and with the quality stream on one handle, the
+result as a MinHashSet whose compare blocks (at most 24 x 24, a num cut and a max_hash cut) are held to `_mhset_model.block`, and one
+record sketched alone by KmerMinHash beside its own row; at k = 32 with a scaled rule the batch holds the k-mer whose hash IS the
+threshold, alone and inside a long record.  `kmer_sets` / `kmer_sets_wide`: two sets extracted from tables (the query batch, the
+reference set), compare, totals, every op and rule, one chained op on a result nobody read back.  `dbg`: the graph of the reference
+set's k-mers (with one periodic read each of DBG_UNITS, two isolated cycles), and its unitig batch handed on, as device tensors, to a
+fresh count table, ReadAbundance and RecordMinHash.  `colors`: an index built colour by colour through tables, sets and per-key masks,
+the batch screened, and the trimmer's compacted device batch screened as it is.  The chains keep every buffer on the device.
 
 Excluded inputs (what a header rules out is not generated for that stage):
   * bytes of the pre-step's "deleted" class inside a record - needletail_amd.h, "Device batch layout: ... no bytes of the pre-step's
     'deleted' class inside a record (the packer, ntk_batch_append, removed them)": none for PRE_NONE, CR / LF for PRE_STRIP_RETURNS,
     space / tab / CR / LF for PRE_NORMALIZE*; `junk_bytes(pre)` leaves them out.  The records' own break byte is the packer's '\\n';
-  * PATH_BYTES_CANONICAL with PRE_NONE / PRE_STRIP_RETURNS - needletail_amd_count.h, _abundance.h, _trim.h, _minhash.h: "Byte-path
-    input that was not normalised ... is NTK_ERR_UNSUPPORTED": `_count_helpers.PATH_PRES` has no such pair;
+  * PATH_BYTES_CANONICAL with PRE_NONE / PRE_STRIP_RETURNS - needletail_amd_count.h, _abundance.h, _trim.h, _minhash.h,
+    _record_minhash.h, _colors.h: "Byte-path input that was not normalised ... is NTK_ERR_UNSUPPORTED": `_count_helpers.PATH_PRES` has
+    no such pair;
   * k = 33..63 on a bit path, and on the abundance and trim libraries - needletail_amd_abundance.h / _trim.h: "k = 33..63 ... is not
-    served here"; the wide stages draw PATH_BYTES_CANONICAL with PRE_NORMALIZE / PRE_NORMALIZE_IUPAC only;
+    served here"; the wide stages draw PATH_BYTES_CANONICAL with PRE_NORMALIZE / PRE_NORMALIZE_IUPAC only; k > 32 outside
+    `kmer_sets_wide` and the two older wide stages - needletail_amd_record_minhash.h and needletail_amd_colors.h hold k = 1..32,
+    needletail_amd_dbg.h odd k = 3..31;
+  * PATH_BITS sets and even k for the graph - needletail_amd_dbg.h: the list holds canonical k-mers of odd k (a k-mer of even k can
+    be its own reverse complement); the binding refuses both, and the `dbg` stage draws DBG_KS on DBG_PATH_PRES;
   * offsets that are not the packer's - needletail_amd_abundance.h: "d_offsets[0] = 0, d_offsets[n_records] = n_bytes, record r = the
-    bytes [d_offsets[r], d_offsets[r + 1]) whose last byte is the record's break byte": offsets are always `_trim_model.offsets`;
+    bytes [d_offsets[r], d_offsets[r + 1]) whose last byte is the record's break byte": offsets are always `_trim_model.offsets`, or
+    what ReadTrimmer.compact_device and KmerGraph.unitig_batch wrote;
   * a foreign MinHash sketch coarser than the handle - needletail_amd_minhash.h: "The counts stay exact when the other sketch keeps
     at least what this one would: the same num or a larger one, the same scaled or a divisor of it".
 The 64 Mi-base chunk seams and batches above 2^32 bytes stay with the tests that own them."""
+import hashlib
+
 import numpy as np
 
 import needletail_amd as nt
 import _abundance_model as A
+import _colors_model as KM
+import _count_model as CM
+import _dbg_model as DM
+import _kmer_sets_model as KS_
+import _mhset_model as SM
 import _minhash_model as M
+import _record_minhash_model as RM
 import _sketch_model as S
 import _trim_model as T
 from _count_helpers import M64, PATH_PRES, oracle_items, oracle_values, pack, quality_masked, upload
 
 BYTES, BITS, BITS_CANON = nt.PATH_BYTES_CANONICAL, nt.PATH_BITS, nt.PATH_BITS_CANONICAL
-STAGES = ("count", "count_wide", "minhash", "minhash_wide", "abundance", "trim")
-WIDE_STAGES = ("count_wide", "minhash_wide")
+OLD_STAGES = ("count", "count_wide", "minhash", "minhash_wide", "abundance", "trim")
+NEW_STAGES = ("record_minhash", "kmer_sets", "kmer_sets_wide", "dbg", "colors")
+STAGES = OLD_STAGES + NEW_STAGES   # a stage's index seeds its cases: new stages go at the end
+WIDE_STAGES = ("count_wide", "minhash_wide", "kmer_sets_wide")
 KS = (1, 2, 3, 15, 16, 17, 21, 31, 32)
 WIDE_KS = (33, 34, 47, 48, 49, 62, 63)
 WIDE_PRES = (nt.PRE_NORMALIZE, nt.PRE_NORMALIZE_IUPAC)
@@ -47,11 +77,21 @@ BUFFERS = (64, 65, 100, 256, 4096, 0)
 MIN_COUNTS_ABUNDANCE = (0, 1, 2, 3)
 MIN_COUNTS_TRIM = (1, 2, 3)
 MODES = (T.PREFIX, T.LONGEST)
+RMH_NUMS = (1, 2, 16, 64, 500, 1 << 20)
+RMH_BUFFERS = (256, 257, 4096, 0)
+DBG_KS = (3, 15, 17, 21, 31)
+DBG_PATH_PRES = tuple(pp for pp in PATH_PRES if pp[0] != BITS)
+DBG_UNITS = (b"AACGT", b"AAACCGGTTTAG")   # no rotation of either is its own reverse complement: a periodic read of one is an isolated cycle
+N_COLORS = (1, 2, 3, 8, 63, 64)
+ROUTES = ("table", "set", "masks")
+COMPARE_SIDE = 24                # MinHashSet.compare is held to the Python model on at most 24 x 24 pairs
+RMH_EDGE_MAX = 5000              # the num-dependent record lengths of the record_minhash stage stay at or below this many windows
 
 # the fixed slices of the GPU suite: stage -> (seed, cases).  tests/test_lib_fuzz_inputs.py proves on the CPU that each meets its
 # conditions; the counts are the smallest at which they do (seeds 100..139 were searched per stage)
 SLICES = {"count": (103, 3), "count_wide": (111, 3), "minhash": (134, 8), "minhash_wide": (131, 10), "abundance": (104, 3),
-          "trim": (111, 4)}
+          "trim": (111, 4), "record_minhash": (113, 8), "kmer_sets": (117, 3), "kmer_sets_wide": (133, 2), "dbg": (127, 4),
+          "colors": (130, 4)}
 
 LANE_RUN = S.LANE_RUN            # kLaneRun (ntk_wide_count.hip, ntk_sketch.hip, ntk_wide_walk.hpp): window ends per lane
 LONG_PIECES_BYTES = 2048 * 16    # kLongPieces (ntk_trim.hip) 16-byte pieces: beyond it a record goes to rt_copy_long_kernel
@@ -68,8 +108,13 @@ WHITESPACE = b" \t\r\n"
 DELETED = {nt.PRE_NONE: b"", nt.PRE_STRIP_RETURNS: b"\r\n", nt.PRE_NORMALIZE: WHITESPACE, nt.PRE_NORMALIZE_IUPAC: WHITESPACE}
 
 
-def edge_lengths(k: int) -> dict:
-    """name -> record length L, each from a constant of the kernels (w = candidate windows, L = w + k - 1)."""
+def rmh_want(num: int) -> int:
+    return 2 * num + 16          # rmh_want of ntk_rmh_rule.hpp
+
+
+def edge_lengths(k: int, stage: str = "count", num: int = 0) -> dict:
+    """name -> record length L, each from a constant of the kernels (w = candidate windows, L = w + k - 1).  The six first stages share
+    one dict; `colors` and `record_minhash` add what their own constants name (`num`: the bottom-s size of a record_minhash case)."""
     e = {
         "0": 0, "1": 1,                                       # the empty record (one break byte) and the shortest one
         "k-2": max(k - 2, 0), "k-1": k - 1,                   # no window
@@ -89,10 +134,46 @@ def edge_lengths(k: int) -> dict:
         e[f"L{L}"] = L
     for w in (2047, 2048, 2049):  # kGroup * kGroupRounds = 32 plane words of 64 window ends: the lane group and the whole wave
         e[f"w{w}"] = w + k - 1
+    if stage == "colors":
+        for w in (63, 64, 65):    # one round of a wave of ntk_colors.hip's record kernel
+            e[f"w{w}"] = w + k - 1
+        for w in (127, 128, 129):  # two rounds
+            e[f"w{w}"] = w + k - 1
+    if stage == "record_minhash":
+        for w in (4095, 4096, 4097):   # kSegment of ntk_record_minhash.hip (kTile = 256 is w255 .. w257 above)
+            e[f"w{w}"] = w + k - 1
+        if num:                   # the all-pass length kRmhAllPass * num and rmh_want(num) of ntk_rmh_rule.hpp
+            for name, w in (("4num-1", 4 * num - 1), ("4num", 4 * num), ("4num+1", 4 * num + 1), ("want-1", rmh_want(num) - 1),
+                            ("want+1", rmh_want(num) + 1)):
+                if w <= RMH_EDGE_MAX:
+                    e[name] = w + k - 1
     return e
 
 
 LONG_CLASSES = ("long_pieces", "long_record")   # kLongPieces * 16 bytes +- 17; kLongRecord + k - 1 +- 1 bases
+COLORS_LONG = "colors_long"                     # kLongRecord of ntk_colors.hip (KM.LONG_RECORD) - 1, + 0, + 1 windows
+ALL_LONG_CLASSES = LONG_CLASSES + (COLORS_LONG,)
+
+
+def long_classes(stage: str) -> tuple:
+    """The long record classes a stage draws: the tables of kmer_sets and dbg take what `count` has covered."""
+    if stage in ("kmer_sets", "kmer_sets_wide", "dbg"):
+        return ()
+    return ("long_pieces", COLORS_LONG) if stage == "colors" else LONG_CLASSES
+
+
+TAU_CLASSES = ("tau_alone", "tau_inside")   # a k-mer whose hash IS the scaled threshold: a record of its own, and inside a long record
+TAU_INSIDE = 800                            # bases of the long one, the k-mer in its middle: more than a 256-end tile on either side
+
+
+def tau_kmer(path: int, scaled: int):
+    """The 32-mer whose hash is exactly max_hash(scaled), as bases, or None where its reverse complement is the canonical strand (a
+    canonical path emits the other key then).  Only k = 32 spans every 64-bit key."""
+    key = int(CM.fmix64_inv(np.uint64(M.max_hash(scaled)))) ^ S.XOR   # `_sketch_model.hash_keys` is fmix64(key ^ XOR)
+    text = "".join("ACGT"[(key >> (2 * (31 - j))) & 3] for j in range(32))
+    if path != BITS and DM.rc(text) < text:
+        return None
+    return text.encode()
 
 
 def junk_bytes(pre: int) -> np.ndarray:
@@ -106,8 +187,8 @@ class Case:
     the table counts.  kinds / classes / starts: per record, its content kind, its edge-length class (None: a random length) and
     its first byte's offset in the packed batch."""
 
-    def __init__(self, k, path, pre):
-        self.k, self.path, self.pre = k, path, pre
+    def __init__(self, k, path, pre, stage="count", extra=None):
+        self.k, self.path, self.pre, self.stage, self.extra = k, path, pre, stage, extra or {}
         self.records, self.quals, self.qbreaks, self.kinds, self.classes = [], [], [], [], []
         self.cutoff, self.ref_records = 0, []
 
@@ -123,6 +204,12 @@ class Case:
 
     def starts(self) -> np.ndarray:
         return self.offsets()[:-1].astype(np.int64)
+
+    def num(self) -> int:
+        return self.extra.get("kind", {}).get("num", 0)
+
+    def edges(self) -> dict:
+        return edge_lengths(self.k, self.stage, self.num())
 
     def tag(self) -> str:
         return f"k {self.k} path {self.path} pre {self.pre} cutoff {self.cutoff} records {len(self.records)} bytes {len(self.buf())}"
@@ -201,21 +288,28 @@ def _qualities(rng, L, cutoff, rate):
     return q
 
 
-def make_case(rng, k, path, pre, budget=None, allow_long=True) -> Case:
+def make_case(rng, k, path, pre, budget=None, allow_long=True, stage="count", extra=None) -> Case:
     """One case for (k, path, pre).  See the module docstring."""
     wide = k > 32
-    c = Case(k, path, pre)
+    c = Case(k, path, pre, stage, extra)
     c.cutoff = 0 if rng.random() < 0.15 else int(rng.integers(33, 76))
     rate = float(rng.choice([0.002, 0.01, 0.05]))
     genome = ACGT[rng.integers(0, 4, int(rng.integers(2000, 4001)))]
-    edges = edge_lengths(k)
+    edges = c.edges()
     names = list(edges)
     budget = int(rng.integers(6000, 20001)) if budget is None else budget
     plan = []   # (class, L)
-    if allow_long and rng.random() < 0.3:
+    longs = long_classes(stage) if allow_long else ()
+    if "long_pieces" in longs and rng.random() < 0.3:
         plan.append(("long_pieces", LONG_PIECES_BYTES + int(rng.integers(-17, 18))))
-    if allow_long and rng.random() < 0.12:
+    if "long_record" in longs and rng.random() < 0.12:
         plan.append(("long_record", LONG_RECORD + k - 1 + int(rng.integers(-1, 2))))
+    if COLORS_LONG in longs and rng.random() < 0.5:
+        plan.append((COLORS_LONG, KM.LONG_RECORD + k - 1 + int(rng.integers(-1, 2))))
+    kind_ = c.extra.get("kind", {})
+    tau = tau_kmer(path, kind_["scaled"]) if stage == "record_minhash" and k == 32 and "scaled" in kind_ else None
+    if tau is not None:
+        plan += [("tau_alone", 32), ("tau_inside", TAU_INSIDE)]
     used = 0
     while used < budget:
         if rng.random() < 0.6:
@@ -236,9 +330,14 @@ def make_case(rng, k, path, pre, budget=None, allow_long=True) -> Case:
             _append(c, rng, np.full(pad, ord("N"), dtype=np.uint8), "spacer", None, rate)
             at += pad + 1
         kind = KINDS[int(rng.choice(len(KINDS), p=KIND_WEIGHTS))]
-        if cls in LONG_CLASSES and kind in ("clean", "periodic"):
+        if cls in ALL_LONG_CLASSES and kind in ("clean", "periodic"):
             kind = "genome"   # a long record of foreign or one-key content says nothing about abundance and costs a hot key
-        _append(c, rng, _content(rng, kind, L, k, pre, genome, at, wide), kind, cls, rate)
+        content = _content(rng, kind, L, k, pre, genome, at, wide)
+        if cls in TAU_CLASSES:   # the planted k-mer alone, or in the middle of a read of the genome
+            kind = "genome"
+            content = _genome_read(rng, genome, L, err=0.0)
+            content[(L - 32) // 2:(L - 32) // 2 + 32] = np.frombuffer(tau, dtype=np.uint8)
+        _append(c, rng, content, kind, cls, rate)
         at += L + 1
     # the reference set: other reads of the same genome at another coverage, a few foreign reads, exact duplicates of query records,
     # a periodic read per unit now and then (hot keys the table holds), and T^40 at k = 32 (the key the table keeps in a side word)
@@ -254,6 +353,9 @@ def make_case(rng, k, path, pre, budget=None, allow_long=True) -> Case:
             c.ref_records.append(bytes(np.resize(np.frombuffer(unit, dtype=np.uint8), 2 * k + int(rng.integers(0, 30)))))
     if k == 32 and rng.random() < 0.5:
         c.ref_records.append(b"T" * 40)
+    if stage == "dbg":   # the graph's input alone: a periodic read per unit of DBG_UNITS, each a cycle of its own
+        for unit in DBG_UNITS:
+            c.ref_records.append(bytes(np.resize(np.frombuffer(unit, dtype=np.uint8), 2 * k + len(unit) + int(rng.integers(0, 30)))))
     return c
 
 
@@ -268,8 +370,19 @@ def _append(c, rng, a, kind, cls, rate):
 def draw_params(rng, stage):
     if stage in WIDE_STAGES:
         return int(rng.choice(WIDE_KS)), BYTES, int(rng.choice(WIDE_PRES))
+    if stage == "dbg":
+        path, pre = DBG_PATH_PRES[int(rng.integers(0, len(DBG_PATH_PRES)))]
+        return int(rng.choice(DBG_KS)), path, pre
     path, pre = PATH_PRES[int(rng.integers(0, len(PATH_PRES)))]
     return int(rng.choice(KS)), path, pre
+
+
+def draw_extra(rng, stage) -> dict:
+    """What a new stage fixes before its records are made: the sketch rule of a record_minhash case, whose num names edge lengths."""
+    if stage != "record_minhash":
+        return {}
+    kind = dict(num=int(rng.choice(RMH_NUMS))) if rng.random() < 0.5 else dict(scaled=int(rng.choice(SCALEDS)))
+    return dict(kind=kind, buffer_entries=int(rng.choice(RMH_BUFFERS)))
 
 
 def case_rng(seed, stage, it):
@@ -281,7 +394,22 @@ def draw_case(seed, stage, it):
     """(rng, case) of iteration `it`: the rng has made the case and goes on to the checker's own draws."""
     rng = case_rng(seed, stage, it)
     k, path, pre = draw_params(rng, stage)
-    return rng, make_case(rng, k, path, pre)
+    if stage in OLD_STAGES:
+        return rng, make_case(rng, k, path, pre)
+    return rng, make_case(rng, k, path, pre, stage=stage, extra=draw_extra(rng, stage))
+
+
+def slice_digest(stage) -> str:
+    """SHA-256 over every case of the stage's slice: packed batch, quality stream, packed reference set and parameters, each with its
+    length in front."""
+    h = hashlib.sha256()
+    seed, n = SLICES[stage]
+    for it in range(1, n + 1):
+        _, c = draw_case(seed, stage, it)
+        for part in (c.buf(), c.qual_stream().tobytes(), pack(c.ref_records), repr((c.k, c.path, c.pre, c.cutoff)).encode()):
+            h.update(len(part).to_bytes(8, "little"))
+            h.update(part)
+    return h.hexdigest()
 
 
 # ---- the models' side -------------------------------------------------------------------------------------------------------------------
@@ -351,14 +479,162 @@ def split_records(case, pieces: int):
     return bytes(seq), np.frombuffer(bytes(qual), dtype=np.uint8), cuts
 
 
+def compacted_records(case, rows, want):
+    """The model's compacted batch as records: (records, quality bytes, the bytes under the break bytes) of `_trim_model.compact`'s
+    result `want` for the trimmer's `rows`."""
+    src = [int(s) for s in want[3]]
+    o_recs = [case.records[s][int(rows[s][0]):int(rows[s][0] + rows[s][1])] for s in src]
+    o_quals = [case.quals[s][int(rows[s][0]):int(rows[s][0] + rows[s][1])] for s in src]
+    return o_recs, o_quals, [case.qbreaks[s] for s in src]
+
+
+def _draw_range(rng, n: int):
+    """A range of at most COMPARE_SIDE of n sketches: (first, end)."""
+    count = int(rng.integers(1, min(COMPARE_SIDE, n) + 1))
+    first = int(rng.integers(0, n - count + 1))
+    return first, first + count
+
+
+def draw_rmh(rng, case) -> dict:
+    """The checker's draws of a record_minhash case (its rule and buffer were drawn before the records: `draw_extra`)."""
+    n = len(case.records)
+    return dict(prefix=int(rng.integers(1, n + 1)), prefix_q=bool(rng.random() < 0.5), abundance=bool(rng.random() < 0.5),
+                num_cut=int(rng.choice((1, 2, 16, 500, 2048, 2049))), hash_cut=float(rng.random()), rows=_draw_range(rng, n),
+                cols=_draw_range(rng, n), probe=int(rng.integers(0, n)), trim=bool(rng.random() < 0.3))
+
+
+def rmh_values(case, use_q: bool):
+    return [RM.record_values(r, case.k, case.path, case.pre, case.quals[i] if use_q else None, case.cutoff)
+            for i, r in enumerate(case.records)]
+
+
+def csr_sketches(csr):
+    """The (hashes, counts) pairs of a CSR of sketches."""
+    off, _, h, c = csr
+    return [(h[int(off[r]):int(off[r + 1])], c[int(off[r]):int(off[r + 1])]) for r in range(off.size - 1)]
+
+
+def hash_cut_of(sketches, u: float) -> int:
+    """The max_hash cut of a compare: the hash at quantile u of the compared rows' hashes, so that it cuts inside them."""
+    pool = np.concatenate([h for h, _ in sketches]) if sketches else np.zeros(0, dtype=np.uint64)
+    return int(np.sort(pool)[int(u * pool.size)]) if pool.size else M.ALL // 2
+
+
+RULE_NAMES = {KS_.MIN: "min", KS_.MAX: "max", KS_.SUM: "sum", KS_.LEFT: "left", KS_.RIGHT: "right"}
+
+
+def draw_ksets(rng) -> dict:
+    ops = [KS_.OPS[int(rng.integers(0, len(KS_.OPS)))] for _ in range(2)]
+    return dict(mc_a=int(rng.integers(1, 4)), mc_b=int(rng.integers(1, 4)), bins=(int(rng.integers(2, 33)), int(rng.integers(2, 9))),
+                ops=ops, left=bool(rng.random() < 0.5), release=bool(rng.random() < 0.3))
+
+
+def ksets_operands(case, d):
+    """The two operands as the model's dicts: the query batch's items and the reference set's, each from its min_count on."""
+    out = []
+    for buf, mc in ((case.buf(), d["mc_a"]), (pack(case.ref_records), d["mc_b"])):
+        keys, counts = items_of(buf, case.k, case.path, case.pre)
+        keep = counts >= mc
+        out.append(KS_.as_dict(keys[keep], counts[keep]))
+    return out
+
+
+def ksets_chain(d, da, db):
+    """The chained step on the model: the result of the first drawn op is an operand of the second."""
+    (op1, rule1), (op2, rule2) = d["ops"]
+    first = KS_.apply(op1, rule1, da, db)
+    return KS_.apply(op2, rule2, first, db) if d["left"] else KS_.apply(op2, rule2, da, first)
+
+
+def draw_dbg(rng) -> dict:
+    return dict(min_count=int(rng.choice((1, 2))), release=bool(rng.random() < 0.3))
+
+
+def dbg_graph(case, d):
+    """(keys, counts, the model's graph) of the reference set's items with count >= min_count."""
+    keys, counts = oracle_items(pack(case.ref_records), case.k, case.path, case.pre)
+    keep = counts >= d["min_count"]
+    return keys[keep], counts[keep].astype(np.uint64), DM.Graph(keys[keep], counts[keep], case.k)
+
+
+def random_masks(rng, n, n_colors):
+    """Masks with no bit, one bit, several, all bits of the index, the last colour's bit, and (below 64 colours) bits beyond it."""
+    bits = KM.color_bits(n_colors)
+    kind = rng.integers(0, 6, n)
+    one = np.uint64(1) << rng.integers(0, n_colors, n).astype(np.uint64)
+    some = (rng.integers(0, 1 << 63, n, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, n, dtype=np.uint64))
+    m = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 4],
+                  [np.zeros(n, np.uint64), one, some & np.uint64(bits), np.full(n, bits, np.uint64), np.full(n, 1 << (n_colors - 1), np.uint64)],
+                  some)   # kind 5: as drawn, bits at or above n_colors among them
+    return m.astype(np.uint64)
+
+
+def draw_colors(rng, case) -> dict:
+    """The checker's draws of a colors case.  groups[c]: the reference records of colour c (record i goes to colour i mod n_colors, and
+    to every other colour with probability min(1 / 2, 1 / n_colors)); routes[c] of ROUTES; star: a colour added through a table whose
+    hits are held to ReadAbundance (None: no table route); dead: a query record of foreign content whose k-mers are added with bits at
+    or above n_colors only (None: 64 colours, or no such record)."""
+    n_colors = int(rng.choice(N_COLORS))
+    nref = len(case.ref_records)
+    member = rng.random((nref, n_colors)) < min(0.5, 1.0 / n_colors)
+    member[np.arange(nref), np.arange(nref) % n_colors] = True
+    routes = [ROUTES[int(rng.integers(0, 3))] for _ in range(n_colors)]
+    tables = [c for c in range(n_colors) if routes[c] == "table"]
+    foreign = [i for i, (r, kind) in enumerate(zip(case.records, case.kinds)) if kind == "clean" and len(r) >= case.k]
+    n = len(case.records)
+    return dict(n_colors=n_colors, groups=[np.flatnonzero(member[:, c]).tolist() for c in range(n_colors)], routes=routes,
+                min_counts=[int(rng.integers(1, 3)) for _ in range(n_colors)], mask_seeds=[int(rng.integers(0, 1 << 31)) for _ in range(n_colors)],
+                star=tables[int(rng.integers(0, len(tables)))] if tables else None,
+                dead=foreign[int(rng.integers(0, len(foreign)))] if foreign and n_colors < KM.COLORS_MAX else None,
+                dead_bit=int(rng.integers(n_colors, KM.COLORS_MAX)) if n_colors < KM.COLORS_MAX else None,
+                prefix=int(rng.integers(1, n + 1)), prefix_q=bool(rng.random() < 0.5), trim=draw_trim(rng, case.k))
+
+
+def colors_steps(case, d):
+    """(model, steps): the index as `_colors_model.Index` and what the device is to add, in order: ("table" | "set", colour, min_count,
+    packed group) for the list routes first, then ("masks", colour, None, (keys, masks)) for the mask routes and the dead keys.  A colour
+    whose group has no k-mer adds nothing."""
+    k, path, pre = case.k, case.path, case.pre
+    model, lists, masks = KM.Index(d["n_colors"]), [], []
+    for c in range(d["n_colors"]):
+        buf = pack([case.ref_records[i] for i in d["groups"][c]])
+        keys, counts = oracle_items(buf, k, path, pre)
+        route, mc = d["routes"][c], d["min_counts"][c]
+        if route == "masks":
+            if keys.size:
+                m = random_masks(np.random.default_rng(d["mask_seeds"][c]), keys.size, d["n_colors"])
+                masks.append(("masks", c, None, (keys, m)))
+        elif (counts >= mc).any():
+            lists.append((route, c, mc, buf))
+            model.add(keys[counts >= mc], 1 << c)
+    if d["dead"] is not None:
+        keys = np.unique(KM.record_values(case.records[d["dead"]], k, path, pre))
+        if keys.size:
+            masks.append(("masks", None, None, (keys, np.full(keys.size, 1 << d["dead_bit"], dtype=np.uint64))))
+    for _, _, _, (keys, m) in masks:
+        model.add(keys, m)
+    return model, lists + masks
+
+
+def colors_values(case, use_q: bool):
+    return [KM.record_values(r, case.k, case.path, case.pre, case.quals[i] if use_q else None, case.cutoff) for i, r in enumerate(case.records)]
+
+
+def trim_chain(case, items, setting):
+    """(rows, compact) of the model for the setting a chain compacts, with the quality mask: `_trim_model.rows` and `.compact`."""
+    mode, mc, ml = setting
+    rows = T.rows(case.records, items, case.k, case.path, case.pre, mode, mc, ml, case.quals, case.cutoff)
+    return rows, T.compact(case.records, rows, case.quals, case.qbreaks)
+
+
 # ---- the device side --------------------------------------------------------------------------------------------------------------------
 
 class Session:
     """What outlives a case: the context, and per (k, path) one table with its abundance and trim handles, whose scratch grows and
-    shrinks from case to case."""
+    shrinks from case to case; likewise one handle per (stage, k, path, ...) of the newer libraries (`handle`)."""
 
     def __init__(self, ctx):
-        self.ctx, self.handles = ctx, {}
+        self.ctx, self.handles, self.others = ctx, {}, {}
 
     def table(self, k, path):
         if (k, path) not in self.handles:
@@ -375,10 +651,27 @@ class Session:
         self.ctx.synchronize()
         return t, ra, rt, oracle_items(buf, case.k, case.path, case.pre)
 
+    def handle(self, key, make):
+        """The handle kept under `key` (a tuple that begins with what it is for), made by `make()` on first use."""
+        if key not in self.others:
+            self.others[key] = make()
+        return self.others[key]
+
+    def rmh(self, stage, k, path, kind, buffer_entries):
+        return self.handle((stage, "rmh", k, path, tuple(kind.items()), buffer_entries),
+                           lambda: nt.RecordMinHash(k, path, ctx=self.ctx, buffer_entries=buffer_entries, **kind))
+
+    def scratch_table(self, stage, k, path):
+        """A second table of (k, path): what a stage counts besides the reference set (narrow or wide by k)."""
+        cls = nt.KmerTable if k <= 32 else nt.WideKmerTable
+        return self.handle((stage, "table", k, path), lambda: cls(k, path, TABLE_CAPACITY, self.ctx))
+
     def close(self):
+        for h in self.others.values():
+            h.close()
         for t, ra, rt in self.handles.values():
             rt.close(); ra.close(); t.close()
-        self.handles = {}
+        self.handles, self.others = {}, {}
 
 
 class Mismatch(AssertionError):
@@ -557,10 +850,8 @@ def check_trim(sess, case, rng):
     if n_out == 0:
         return what
     # the model's compacted records; the device tensors go on as they are
-    src = [int(s) for s in want[3]]
-    o_recs = [recs[s][int(want_rows[s][0]):int(want_rows[s][0] + want_rows[s][1])] for s in src]
-    o_quals = [case.quals[s][int(want_rows[s][0]):int(want_rows[s][0] + want_rows[s][1])] for s in src]
-    o_buf, o_qs = pack(o_recs), stream(o_quals, [case.qbreaks[s] for s in src])
+    o_recs, o_quals, o_breaks = compacted_records(case, want_rows, want)
+    o_buf, o_qs = pack(o_recs), stream(o_quals, o_breaks)
     assert o_buf == want[0][:want[1]]
     with nt.KmerTable(k, path, max(want[1], 16), sess.ctx) as fresh:
         fresh.count_device(out[0], out[1], pre, d_qual=out[4], quality_cutoff=cutoff)
@@ -577,8 +868,250 @@ def check_trim(sess, case, rng):
     return what
 
 
+def _eq_csr(got, want, what):
+    for name, g, w in zip(("offsets", "n_windows", "hashes", "counts"), got, want):
+        _eq(g, w, f"{what} {name}")
+
+
+def _eq_block(got, want, what):
+    """A compare block as tests/test_gpu_minhash_set.py's assert_block holds it: integers, vectors and doubles with array_equal."""
+    for name in SM.MATRICES + ("n_a", "n_b"):
+        if got[name].dtype != want[name].dtype:
+            raise Mismatch(f"{what} {name}: dtype {got[name].dtype} / {want[name].dtype}")
+        _eq(got[name], want[name], f"{what} {name}")
+
+
+def check_record_minhash(sess, case, rng):
+    """Per-record sketches of the batch without the quality stream, of a prefix, and with it, on one handle; then the last result as a
+    sketch set whose compare blocks are held to the model, and one record sketched alone by KmerMinHash beside its own row."""
+    k, path, pre, cutoff = case.k, case.path, case.pre, case.cutoff
+    kind, buffer_entries = case.extra["kind"], case.extra["buffer_entries"]
+    d = draw_rmh(rng, case)
+    what = f"record_minhash {kind} buffer {buffer_entries} {d}"
+    buf, off, n = case.buf(), case.offsets(), len(case.records)
+    dev, dq, d_off = upload(buf, fill=ord("A")), upload(case.qual_stream().tobytes(), fill=0xFF), _dev_u64(off)
+    rmh = sess.rmh(case.stage, k, path, kind, buffer_entries)
+    values = {False: rmh_values(case, False), True: rmh_values(case, True)}
+    q = dict(d_qual=dq, quality_cutoff=cutoff)
+    rmh.run_device(dev, len(buf), d_off, n, pre)
+    _eq_csr(rmh.sketches(), RM.csr(values[False], **kind), what + " whole batch")
+    m = d["prefix"]   # the bytes after the prefix are readable and are not input
+    rmh.run_device(dev, int(off[m]), d_off, m, pre, **(q if d["prefix_q"] else {}))
+    _eq_csr(rmh.sketches(), RM.csr(values[d["prefix_q"]][:m], **kind), what + f" first {m} records")
+    rmh.run_device(dev, len(buf), d_off, n, pre, **q)
+    want = RM.csr(values[True], **kind)
+    _eq_csr(rmh.sketches(), want, what + " whole batch with qualities")
+    # the set behind it
+    sk = csr_sketches(want)
+    s = sess.handle((case.stage, "mhset", d["abundance"]), lambda: nt.MinHashSet(d["abundance"], sess.ctx))
+    s.reset()
+    _eq(list(s.add_record_sketches(rmh)), list(range(n)), what + " indices of the set")
+    (r0, r1), (c0, c1) = d["rows"], d["cols"]
+    for num, max_hash in ((d["num_cut"], M.ALL), (0, hash_cut_of(sk[r0:r1], d["hash_cut"]))):
+        got = s.compare(rows=(r0, r1), cols=(c0, c1), num=num, max_hash=max_hash)
+        _eq_block(got, SM.block(sk[r0:r1], sk[c0:c1], num, max_hash, d["abundance"]), what + f" compare num {num} max_hash {max_hash}")
+    # one record alone through KmerMinHash: its row is the record's own
+    r = d["probe"]
+    one, one_q = upload(case.records[r] + b"\n"), upload(bytes(case.quals[r]) + bytes([case.qbreaks[r]]), fill=0xFF)
+    with nt.KmerMinHash(k, path, ctx=sess.ctx, **kind) as mh:
+        mh.add_device(one, len(case.records[r]) + 1, pre, d_qual=one_q, quality_cutoff=cutoff)
+        idx = s.add(mh)
+    _eq(idx, n, what + " index of the added sketch")
+    alone, own = s.compare(rows=idx, cols=(0, n)), s.compare(rows=r, cols=(0, n))
+    for name in SM.MATRICES + ("n_a", "n_b"):
+        _eq(alone[name], own[name], what + f" record {r} alone, {name}")
+    if d["trim"]:
+        rmh.trim()
+    return what
+
+
+def _apply_op(a, b, op, rule):
+    if op == KS_.INTERSECT:
+        return a.intersect(b, RULE_NAMES[rule])
+    if op == KS_.UNION:
+        return a.union(b, RULE_NAMES[rule])
+    return a.subtract(b) if op == KS_.SUBTRACT else a.counters_subtract(b)
+
+
+def _eq_set(got, want: dict, what):
+    keys, counts = got.items()
+    wk, wc = KS_.as_list(want, got.key_words)
+    _eq(len(got), len(want), what + " length")
+    _eq(keys, wk, what + " keys")
+    _eq(counts, wc, what + " counts")
+    _eq(got.violations(), 0, what + " violations")
+
+
+def check_kmer_sets(sess, case, rng):
+    """Two sets extracted from tables (the query batch's and the session table's, which counted the reference set): compare, totals,
+    every op and rule, and one chained step whose middle result stays on the device."""
+    k, path, pre = case.k, case.path, case.pre
+    d = draw_ksets(rng)
+    what = f"kmer_sets {d}"
+    da, db = ksets_operands(case, d)
+    buf, ref = case.buf(), pack(case.ref_records)
+    ta, tb = sess.scratch_table(case.stage, k, path), sess.scratch_table(case.stage + " reference", k, path)
+    devs = [upload(buf), upload(ref)]   # both stay until the context's stream has read them
+    for t, b, dev in ((ta, buf, devs[0]), (tb, ref, devs[1])):
+        t.reset()
+        t.count_device(dev, len(b), pre)
+    sess.ctx.synchronize()
+    with nt.KmerSet.from_table(ta, d["mc_a"]) as a, nt.KmerSet.from_table(tb, d["mc_b"]) as b:
+        _eq_set(a, da, what + " the query batch's set")
+        _eq_set(b, db, what + " the reference set's set")
+        hist, totals = a.compare(b, *d["bins"])
+        want_hist, want_totals = KS_.compare(da, db, *d["bins"])
+        _eq(hist.reshape(-1), want_hist, what + " hist")
+        _eq(totals == want_totals, True, what + f" totals {totals} / {want_totals}")
+        _eq(a.totals(b) == KS_.compare(da, db, 2, 2)[1], True, what + " totals of a 2 x 2 compare")
+        for op, rule in KS_.OPS:
+            with _apply_op(a, b, op, rule) as out:
+                _eq_set(out, KS_.apply(op, rule, da, db), what + f" op {op} rule {rule}")
+        (op1, rule1), (op2, rule2) = d["ops"]
+        with _apply_op(a, b, op1, rule1) as first:   # not read back: the second op takes it from the device
+            with (_apply_op(first, b, op2, rule2) if d["left"] else _apply_op(a, first, op2, rule2)) as second:
+                _eq_set(second, ksets_chain(d, da, db), what + " chained")
+        if d["release"]:
+            a.release()
+    return what
+
+
+def hold_graph(g, m, n_keys: int, name):
+    """Everything a KmerGraph answers, held to the model `m` of its list (tests/test_gpu_dbg.py's `hold`).  Returns (stats, the unitig
+    batch as the graph handed it out)."""
+    edges, totals = g.edges().cpu().numpy(), g.totals()
+    u = g.unitigs()
+    seq, n_bytes, offsets, n_records = g.unitig_batch()
+    stats = g.stats()
+    assert np.array_equal(edges, m.edges), name
+    want = m.totals()
+    for key in DM.TOTALS:
+        assert np.array_equal(totals[key], want[key]), (name, key, totals[key], want[key])
+    assert (u.n_unitigs, u.n_bases) == (m.n_unitigs, m.n_bases), name
+    assert np.array_equal(u.kmer_rows.cpu().numpy().view(np.uint32), m.kmer_rows), name
+    assert np.array_equal(u.unitig_rows.cpu().numpy().view(np.uint64), m.unitig_rows), name
+    assert int(m.unitig_rows[:, 1].sum()) == n_keys
+    text, off = m.batch()
+    assert n_bytes == int(off[-1]) and n_records == m.n_unitigs, name
+    assert np.array_equal(offsets.cpu().numpy().view(np.uint64), off), name
+    assert np.array_equal(seq[: text.size].cpu().numpy(), text), name
+    assert bool((seq[text.size:] == ord("\n")).all()), name
+    return stats, (seq, n_bytes, offsets, n_records)
+
+
+def check_dbg(sess, case, rng):
+    """The graph of the reference set's k-mers from a min_count on, and its unitig batch handed unchanged to a fresh count table, the
+    abundance call and the per-record sketches."""
+    k, path, pre = case.k, case.path, case.pre
+    d = draw_dbg(rng)
+    mc = d["min_count"]
+    what = f"dbg {d}"
+    t, ra, rt, items = sess.counted(case)
+    keys, counts, m = dbg_graph(case, d)
+    with nt.KmerSet.from_table(t, mc) as s, nt.KmerGraph(s) as g:
+        _eq(s.items()[0], keys, what + " keys of the set")
+        _, (seq, n_bytes, offsets, n_records) = hold_graph(g, m, len(keys), what)
+        if d["release"]:
+            g.release()
+        if n_records == 0:
+            return what
+        spelled = [u.encode() for u in m.spelled]
+        with nt.KmerTable(k, path, max(n_bytes, 16), sess.ctx) as fresh:
+            fresh.count_device(seq, n_bytes, pre)
+            got = fresh.items()
+            _eq(got[0], keys, what + " recount keys")
+            _eq(got[1], np.ones(len(keys), dtype=np.uint64), what + " recount counts")
+        rows = _host(ra.run_device(seq, n_bytes, offsets, n_records, pre, min_count=mc))
+        _eq(rows, A.rows(spelled, items, k, path, pre, mc), what + " abundance of the unitigs")
+        _eq(rows[:, 1], rows[:, 0], what + " every k-mer of a unitig is present")
+        _eq(rows[:, 0], m.unitig_rows[:, 1], what + " k-mers per unitig")
+        rmh = sess.rmh(case.stage, k, path, dict(scaled=1), 0)
+        rmh.run_device(seq, n_bytes, offsets, n_records, pre)
+        got = rmh.sketches()
+        _eq_csr(got, RM.sketches(spelled, k, path, pre, scaled=1), what + " sketches of the unitigs")
+        _eq(np.diff(got[0].astype(np.int64)), m.unitig_rows[:, 1].astype(np.int64), what + " hashes per unitig")
+    return what
+
+
+def _eq_screen(got, want, what):
+    for name, g, w in zip(("rows", "hits", "single"), got, want):
+        if g is not None:
+            _eq(_host(g), w, f"{what} {name}")
+
+
+def check_colors(sess, case, rng):
+    """An index built colour by colour through tables, sets and per-key masks; the batch screened with and without the quality stream and
+    d_single, a prefix, the census; then the trimmer's compacted device batch screened as it is."""
+    k, path, pre, cutoff = case.k, case.path, case.pre, case.cutoff
+    d = draw_colors(rng, case)
+    model, steps = colors_steps(case, d)
+    what = f"colors n_colors {d['n_colors']} routes {d['routes']} star {d['star']} dead {d['dead']} trim {d['trim']}"
+    recs, buf, off, n = case.records, case.buf(), case.offsets(), len(case.records)
+    dev, dq, d_off = upload(buf), upload(case.qual_stream().tobytes(), fill=0xFF), _dev_u64(off)
+    q = dict(d_qual=dq, quality_cutoff=cutoff)
+    values = {False: colors_values(case, False), True: colors_values(case, True)}
+    kc = sess.handle((case.stage, "colors", k, path, d["n_colors"]), lambda: nt.KmerColors(k, path, d["n_colors"], TABLE_CAPACITY, sess.ctx))
+    kc.reset()
+    scratch = sess.scratch_table(case.stage, k, path)
+    star_t = star_ra = None
+    try:
+        lists = [st for st in steps if st[0] != "masks"]
+        for route, c, mc, gbuf in lists:
+            t = scratch
+            if c == d["star"]:
+                t = star_t = nt.KmerTable(k, path, max(len(gbuf), 16), sess.ctx)
+            t.reset()
+            g_dev = upload(gbuf)
+            t.count_device(g_dev, len(gbuf), pre)
+            sess.ctx.synchronize()
+            if route == "table":
+                kc.add(t, c, mc)
+            else:
+                with nt.KmerSet.from_table(t, mc) as ks:
+                    kc.add(ks, c)
+        if star_t is not None:   # before any mask is added: colour `star` is the table's keys with count >= its min_count
+            star_ra = nt.ReadAbundance(star_t)
+            hits = _host(kc.run_device(dev, len(buf), d_off, n, pre, single=False)[1])
+            present = _host(star_ra.run_device(dev, len(buf), d_off, n, pre, min_count=d["min_counts"][d["star"]]))[:, 1]
+            _eq(hits[:, d["star"]], present, what + " hits of the star colour and n_present of its table")
+        for _, _, _, (keys, masks) in steps[len(lists):]:
+            kc.add_masks(keys, masks)
+    finally:
+        if star_ra is not None:
+            star_ra.close()
+        if star_t is not None:
+            star_t.close()
+    for use_q in (False, True):
+        want = KM.screen_values(values[use_q], model)
+        for single in (True, False):
+            got = kc.run_device(dev, len(buf), d_off, n, pre, single=single, **(q if use_q else {}))
+            _eq_screen(got, want, what + f" quality {use_q} single {single}")
+    m = d["prefix"]
+    got = kc.run_device(dev, int(off[m]), d_off, m, pre, **(q if d["prefix_q"] else {}))
+    _eq_screen(got, KM.screen_values(values[d["prefix_q"]][:m], model), what + f" first {m} records")
+    kc.release()
+    st = kc.stats()
+    _eq([st["n_dropped"], st["n_keys"], st["n_masked_bits"]], [0, model.n_keys, model.n_masked_bits], what + " census")
+    _eq(st["per_color"], model.per_color(), what + " per_color")
+    # the chain: the trimmer's compacted batch, as the device wrote it
+    t, ra, rt, items = sess.counted(case)
+    mode, mc, ml = d["trim"]
+    want_rows, want = trim_chain(case, items, d["trim"])
+    d_rows = rt.run_device(dev, len(buf), d_off, n, pre, min_count=mc, mode=mode, min_length=ml, **q)
+    _eq(_host(d_rows), want_rows, what + " trim rows")
+    out = rt.compact_device(dev, len(buf), d_off, n, d_rows, dq)
+    _eq(out[1], want[1], what + " compacted n_bytes")
+    n_out = len(want[3])
+    if n_out:
+        o_recs, o_quals, _ = compacted_records(case, want_rows, want)
+        got = kc.run_device(out[0], out[1], out[2], n_out, pre, d_qual=out[4], quality_cutoff=cutoff)
+        _eq_screen(got, KM.screen(o_recs, model, k, path, pre, o_quals, cutoff), what + " screen of the compacted batch")
+    return what
+
+
 CHECKERS = {"count": check_count, "count_wide": check_count, "minhash": check_minhash, "minhash_wide": check_minhash,
-            "abundance": check_abundance, "trim": check_trim}
+            "abundance": check_abundance, "trim": check_trim, "record_minhash": check_record_minhash, "kmer_sets": check_kmer_sets,
+            "kmer_sets_wide": check_kmer_sets, "dbg": check_dbg, "colors": check_colors}
 
 
 def run_case(sess, seed, stage, it):
@@ -602,4 +1135,5 @@ def dump(case, path):
     """The case as an .npz: packed query batch, offsets, quality stream, packed reference batch and its offsets, and its parameters."""
     np.savez(path, seq=np.frombuffer(case.buf(), dtype=np.uint8), offsets=case.offsets(), qual=case.qual_stream(),
              ref=np.frombuffer(pack(case.ref_records), dtype=np.uint8), ref_offsets=T.offsets(case.ref_records),
-             params=np.array([case.k, case.path, case.pre, case.cutoff]), kinds=np.array(case.kinds))
+             params=np.array([case.k, case.path, case.pre, case.cutoff]), kinds=np.array(case.kinds), stage=np.array(case.stage),
+             extra=np.array(repr(case.extra)))

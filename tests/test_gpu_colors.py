@@ -17,6 +17,7 @@ from needletail_amd import _lib as NL  # noqa: E402
 from needletail_amd import coloring  # noqa: E402
 import _colors_model as KM  # noqa: E402
 import _count_model as CM  # noqa: E402
+from _lib_fuzz import random_masks  # noqa: E402  (the structured fuzz draws its masks the same way)
 from _count_helpers import CUTOFF, PATH_PRES, pack, quality_masked, random_records, upload  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -72,18 +73,6 @@ def assert_screen(got, want, what):
         if not np.array_equal(g, w):
             bad = np.nonzero((g != w).any(axis=1))[0]
             raise AssertionError((what, name, f"{bad.size} records differ, first {int(bad[0])}", g[bad[0]].tolist(), w[bad[0]].tolist()))
-
-
-def random_masks(rng, n, n_colors):
-    """Masks with no bit, one bit, several, all bits of the index, the last colour's bit, and (below 64 colours) bits beyond it."""
-    bits = KM.color_bits(n_colors)
-    kind = rng.integers(0, 6, n)
-    one = np.uint64(1) << rng.integers(0, n_colors, n).astype(np.uint64)
-    some = (rng.integers(0, 1 << 63, n, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, n, dtype=np.uint64))
-    m = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 4],
-                  [np.zeros(n, np.uint64), one, some & np.uint64(bits), np.full(n, bits, np.uint64), np.full(n, 1 << (n_colors - 1), np.uint64)],
-                  some)   # kind 5: as drawn, bits at or above n_colors among them
-    return m.astype(np.uint64)
 
 
 def indexed(ctx, k, path, n_colors, values, seed):

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import needletail_amd as nt  # noqa: E402
 from needletail_amd import dbg as D  # noqa: E402
 import _dbg_model as DM  # noqa: E402
+from _lib_fuzz import hold_graph  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -46,26 +47,11 @@ def make(ctx, keys, counts, k):
 
 
 def hold(ctx, k, keys, counts, name):
-    """Everything KmerGraph answers for the list, held to the model.  Returns (model, stats)."""
+    """Everything KmerGraph answers for the list, held to the model (`_lib_fuzz.hold_graph`, which the structured fuzz shares).  Returns
+    (model, stats)."""
     m = DM.Graph(keys, counts, k)
     with nt.KmerGraph(make(ctx, keys, counts, k)) as g:
-        edges, totals = g.edges().cpu().numpy(), g.totals()
-        u = g.unitigs()
-        seq, n_bytes, offsets, n_records = g.unitig_batch()
-        stats = g.stats()
-    assert np.array_equal(edges, m.edges), name
-    want = m.totals()
-    for key in DM.TOTALS:
-        assert np.array_equal(totals[key], want[key]), (name, key, totals[key], want[key])
-    assert (u.n_unitigs, u.n_bases) == (m.n_unitigs, m.n_bases), name
-    assert np.array_equal(u.kmer_rows.cpu().numpy().view(np.uint32), m.kmer_rows), name
-    assert np.array_equal(u.unitig_rows.cpu().numpy().view(np.uint64), m.unitig_rows), name
-    assert int(m.unitig_rows[:, 1].sum()) == len(keys)
-    text, off = m.batch()
-    assert n_bytes == int(off[-1]) and n_records == m.n_unitigs, name
-    assert np.array_equal(offsets.cpu().numpy().view(np.uint64), off), name
-    assert np.array_equal(seq[: text.size].cpu().numpy(), text), name
-    assert bool((seq[text.size:] == ord("\n")).all()), name
+        stats, _ = hold_graph(g, m, len(keys), name)
     return m, stats
 
 

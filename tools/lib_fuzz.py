@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""Time-budgeted structured differential fuzz of the six k-mer libraries (count table, wide count table, HyperLogLog sketch, read
-abundance, read trimmer and its batch writer, MinHash) against the host models of tests/ - the generator and the checkers are
-tests/_lib_fuzz.py, whose fixed slices run in the suite (tests/test_gpu_lib_fuzz.py).  Needs a gfx950 device, but for --dump.
+"""Time-budgeted structured differential fuzz of the eleven k-mer libraries (count table, wide count table, HyperLogLog sketch, read
+abundance, read trimmer and its batch writer, MinHash, per-record MinHash with the sketch set, k-mer set algebra narrow and wide, the
+de Bruijn graph, the coloured index) against the host models of tests/ - the generator and the checkers are tests/_lib_fuzz.py, whose
+fixed slices run in the suite (tests/test_gpu_lib_fuzz.py).  Needs a gfx950 device, but for --dump.  --stage takes any of
+`_lib_fuzz.STAGES`: count, count_wide, minhash, minhash_wide, abundance, trim, record_minhash, kmer_sets, kmer_sets_wide, dbg, colors.
 
     python tools/lib_fuzz.py --seconds 180 --seed 1 > profiles/lib_fuzz/<name>.log
     python tools/lib_fuzz.py --seed 1 --stage trim --replay-it 17            # the device work of that case alone
     python tools/lib_fuzz.py --seed 1 --stage trim --replay-it 17 --dump case.npz   # its input, without a GPU
+    python tools/lib_fuzz.py --seed 1 --stage colors --replay-it 5 --dump case.npz  # (a newer stage's dump also holds what it drew first)
 
 Iteration N runs case N of every chosen stage; each (seed, stage, N) has a random stream of its own, so a replay draws exactly what
 the run drew.  A mismatch prints "MISMATCH seed S it N stage X (k, path, pre, kinds ...)" and the settings the checker drew."""

@@ -139,6 +139,150 @@ class Graph:
         return np.frombuffer(body + b"\n" * (-len(body) % 16), dtype=np.uint8), off
 
 
+class ArrayGraph:
+    """Graph on arrays, for lists of a million keys: the same attributes but `strings`, `mate`, `link` and `spelled`.  Adjacency is a
+    binary search for the eight neighbours of every key, the links follow from the edge nibbles, and the walk is a plain loop that
+    takes every k-mer once: from the ends of the paths first (the states that lack a link on one side), then around what is left,
+    which lies on cycles.  tests/test_dbg_array_model.py holds it to Graph on every small case; it is trusted through that alone.
+    walk=False stops after the adjacency and the links: `edges` and `totals()` only."""
+
+    def __init__(self, keys, counts, k: int, walk: bool = True):
+        U = np.uint64
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        self.k, self.n = k, int(keys.size)
+        n, mask = self.n, U((1 << (2 * k)) - 1)
+        self.keys, self.counts = keys, np.ascontiguousarray(counts, dtype=np.uint64)
+        # tgt[side][c], flip[side][c]: the k-mer the half-edge (i, side, c) reaches (-1: none) and the side of that k-mer it enters
+        tgt = np.full((2, 4, n), -1, dtype=np.int64)
+        flip = np.zeros((2, 4, n), dtype=np.int64)
+        if n:
+            for side, u in enumerate((keys, _rc_values(keys, k))):
+                for c in range(4):
+                    t = ((u << U(2)) & mask) | U(c)
+                    y = np.minimum(t, _rc_values(t, k))
+                    by_value = np.argsort(y)   # ascending queries walk the list once: several times faster than in the keys' order
+                    at = np.empty(n, dtype=np.int64)
+                    at[by_value] = np.minimum(np.searchsorted(keys, y[by_value]), n - 1)
+                    tgt[side, c] = np.where(keys[at] == y, at, -1)
+                    flip[side, c] = t == y
+        have = tgt >= 0
+        self.edges = np.zeros(n, dtype=np.uint8)
+        for side in range(2):
+            for c in range(4):
+                self.edges |= (have[side, c].astype(np.uint8) << np.uint8(4 * side + c))
+        self.deg = have.sum(axis=1)                                      # [side, i]
+        self.n_self = int((tgt == np.arange(n)[None, None, :]).sum())
+        # links: the one half-edge of a side, to another k-mer, entering a side that has one half-edge too
+        only = np.argmax(have, axis=1)                                   # [side, i]: the c of the first set bit
+        idx = np.arange(n)
+        self.link_to = np.full((2, n), -1, dtype=np.int64)               # the state 2 j + side' entered
+        for side in range(2):
+            j, s2 = tgt[side, only[side], idx], flip[side, only[side], idx]
+            ok = (self.deg[side] == 1) & (j != idx) & (j >= 0)
+            jj = np.where(ok, j, 0)
+            ok &= self.deg[s2, jj] == 1
+            self.link_to[side] = np.where(ok, 2 * j + s2, -1)
+        if walk:
+            self._walk()
+
+    def totals(self) -> dict:
+        hist = np.zeros((5, 5), dtype=np.uint64)
+        np.add.at(hist, (self.deg[0], self.deg[1]), 1)
+        a, b = np.meshgrid(np.arange(5), np.arange(5), indexing="ij")
+        return {"n_half_edges": int(self.deg.sum()), "deg_hist": hist, "n_isolated": int(hist[0, 0]),
+                "n_tips": int(hist[0, 1:].sum() + hist[1:, 0].sum()), "n_branching": int(hist[(a > 1) | (b > 1)].sum()),
+                "n_self": self.n_self, "n_links": int((self.link_to >= 0).sum())}
+
+    def _walk(self):
+        n, k = self.n, self.k
+        has = self.link_to >= 0                                          # [side, i]
+        # the state after (i, out): leave through `out`, enter (j, side'), go on through the other side of j
+        nxt = np.where(self.link_to >= 0, self.link_to ^ 1, -1).T.reshape(-1).tolist()   # by state 2 i + out
+        seen = (~has[0] & ~has[1]).tolist()                              # a k-mer without a link is a unitig by itself, below
+        starts, lengths, cyclic, order = [], [], [], []                  # per unitig; `order`: the states of all of them, in a row
+        ends = np.flatnonzero(has[0] != has[1])
+        for i, out in zip(ends.tolist(), has[1][ends].tolist()):         # out = 1 only where side 1 has the link
+            if seen[i]:
+                continue   # the larger end of a path already walked
+            d, at = 2 * i + out, len(order)
+            while d >= 0:
+                seen[d >> 1] = True
+                order.append(d)
+                d = nxt[d]
+            starts.append(i); lengths.append(len(order) - at); cyclic.append(0)
+        for i in np.flatnonzero(~np.array(seen, dtype=bool) if n else np.zeros(0, bool)).tolist():
+            if seen[i]:
+                continue
+            d, at = 2 * i, len(order)                                    # ascending: i is the cycle's smallest k-mer
+            while not seen[d >> 1]:
+                seen[d >> 1] = True
+                order.append(d)
+                d = nxt[d]
+            assert d == 2 * i, "what no path reaches closes on itself"
+            starts.append(i); lengths.append(len(order) - at); cyclic.append(1)
+        self.walk_steps = len(order)                                     # passes of the two loops' bodies: one per k-mer with a link
+        lone = np.flatnonzero(~has[0] & ~has[1])
+        starts = np.concatenate([np.array(starts, dtype=np.int64), lone])
+        lengths = np.concatenate([np.array(lengths, dtype=np.int64), np.ones(lone.size, dtype=np.int64)])
+        cyclic = np.concatenate([np.array(cyclic, dtype=np.int64), np.zeros(lone.size, dtype=np.int64)])
+        first = np.concatenate([[0], np.cumsum(lengths)])[:-1]           # of each unitig in `order`
+        order = np.concatenate([np.array(order, dtype=np.int64), 2 * lone])
+        assert order.size == n and np.array_equal(np.sort(order >> 1), np.arange(n)), "every k-mer once"
+        # unitigs are numbered by their first k-mer, ascending
+        by_start = np.argsort(starts, kind="stable")
+        starts, lengths, cyclic, first = starts[by_start], lengths[by_start], cyclic[by_start], first[by_start]
+        U = len(starts)
+        new_first = np.concatenate([[0], np.cumsum(lengths)])[:-1].astype(np.int64)
+        take = np.repeat(first - new_first, lengths) + np.arange(n)      # `order` with the unitigs in their final order
+        order = order[take]
+        unit = np.repeat(np.arange(U), lengths)
+        pos = np.arange(n) - np.repeat(new_first, lengths)
+        km, out = order >> 1, order & 1
+        self.kmer_rows = np.zeros((n, 2), dtype=np.uint32)
+        self.kmer_rows[km, 0] = unit
+        self.kmer_rows[km, 1] = pos << 1 | out
+        sums = np.add.reduceat(self.counts[km], new_first) if U else np.zeros(0, dtype=np.uint64)   # (uint64 sums wrap)
+        last = new_first + lengths - 1
+        flags = cyclic | self.deg[1 - out[new_first], km[new_first]] << 8 | self.deg[out[last], km[last]] << 12 if U else np.zeros(0, np.int64)
+        self.unitig_rows = np.stack([starts.astype(np.uint64), lengths.astype(np.uint64), sums.astype(np.uint64),
+                                     flags.astype(np.uint64)], axis=1).reshape(-1, 4)
+        self.n_unitigs, self.n_bases = U, int((lengths + k - 1).sum())
+        # the spelled batch: the first base of every k-mer as the walk reads it, the whole of a unitig's last one, a break byte
+        v = np.where(out == 1, _rc_values(self.keys[km], k), self.keys[km]) if n else np.zeros(0, dtype=np.uint64)
+        self._off = np.concatenate([[0], np.cumsum(lengths + k)]).astype(np.uint64)
+        text = np.full(int(self._off[-1]) + (-int(self._off[-1]) % 16), ord("\n"), dtype=np.uint8)
+        letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+        at = self._off[:-1].astype(np.int64)[unit] + pos
+        text[at] = letters[((v >> np.uint64(2 * (k - 1))) & np.uint64(3)).astype(np.intp)]
+        for j in range(1, k):
+            text[at[last] + j] = letters[((v[last] >> np.uint64(2 * (k - 1 - j))) & np.uint64(3)).astype(np.intp)]
+        self._text = text
+
+    def batch(self):
+        return self._text, self._off
+
+
+def _rc_values(x, k: int) -> np.ndarray:
+    """Reverse complement of packed k-mers (complement = 3 - code; the 2-bit groups reversed)."""
+    x = ~np.asarray(x, dtype=np.uint64)
+    for shift, m in ((2, 0x3333333333333333), (4, 0x0F0F0F0F0F0F0F0F), (8, 0x00FF00FF00FF00FF), (16, 0x0000FFFF0000FFFF)):
+        x = ((x >> np.uint64(shift)) & np.uint64(m)) | ((x & np.uint64(m)) << np.uint64(shift))
+    x = (x >> np.uint64(32)) | (x << np.uint64(32))
+    return x >> np.uint64(64 - 2 * k)
+
+
+def kmers_of_codes(codes, k: int) -> np.ndarray:
+    """The canonical values of every k-mer of one sequence given as base codes 0 .. 3 (not distinct, in the sequence's order)."""
+    codes = np.asarray(codes, dtype=np.uint64)
+    m = codes.size - k + 1
+    if m <= 0:
+        return np.zeros(0, dtype=np.uint64)
+    v = np.zeros(m, dtype=np.uint64)
+    for j in range(k):
+        v = (v << np.uint64(2)) | codes[j:j + m]
+    return np.minimum(v, _rc_values(v, k))
+
+
 # ---- the cases both suites run ----------------------------------------------------------------------------------------------------------
 
 # canonical 3-mers: AAA (a self loop), ACG (targets its own reverse complement), ACA and CAC (linked on both sides: the cycle ACAC), the

@@ -49,6 +49,17 @@ inline unsigned grid_for(uint64_t items, unsigned block) { const uint64_t b = (i
         }                                                \
     } while (0)
 
+}  // namespace
+
+// how the core owns device and pinned memory: the shared layer, with the core's check and status - every failed HIP call, out of memory
+// included, is recorded for ntk_last_hip_error and answered NTK_ERR_HIP
+#define CT_HIPCHK HIPCHK
+#include "ntk_device_mem.hpp"
+
+namespace {
+
+int alloc_status(hipError_t e) { HIPCHK(e); return NTK_OK; }   // (only ever called with a failure)
+
 constexpr uint32_t kLutChanged = 0x100, kLutDeleted = 0x200;
 
 // Byte maps, restated from the reference's match arms.
@@ -90,11 +101,6 @@ void build_complement_lut(uint16_t *lut)
     }
 }
 
-struct Scratch {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
 }  // namespace
 
 // What the device buffers of a CompatBank hold.  The banks serve every batched face in turn, so a slot has one name per role; the slots
@@ -119,9 +125,9 @@ enum BankSlot {
 
 // Everything one in-flight chunk of the batched compat faces owns (run_banked).
 struct CompatBank {
-    void *h_stage = nullptr; size_t h_stage_bytes = 0;   // pinned: record starts + packed bytes (item arrays)
-    uint64_t *h_total = nullptr;                         // pinned: the chunk's item total
-    Scratch d[kBankSlots];
+    Pinned<uint8_t> h_stage;    // record starts + packed bytes (item arrays)
+    Pinned<uint64_t> h_total;   // the chunk's item total
+    DeviceArray<uint8_t> d[kBankSlots];
     template <class T> T *at(BankSlot s) const { return (T *)d[s].p; }
     hipEvent_t ev_ready = nullptr;      // the chunk is uploaded (item arrays: and its item total is in h_total)
     hipEvent_t ev_computed = nullptr;   // its kernels have run: the download may start
@@ -145,9 +151,10 @@ struct ntk_ctx {
     int n_cu = 256;
     int launch_blocks = 0, launch_threads = 0;   // 0 = automatic
     uint64_t *d_acc = nullptr;      // accumulators in use (own or caller-bound)
-    uint64_t *d_acc_own = nullptr;
-    uint32_t *d_part_hist = nullptr;
-    uint32_t *d_work = nullptr;     // kMaxShards work counters, one per 64-B line
+    DeviceArray<uint64_t> d_acc_own;
+    DeviceArray<uint32_t> d_part_hist;      // the partials of a reduce launch, a row per block (ensure_partials): kHistBins bins ...
+    DeviceArray<uint64_t> d_part_scalars;   // ... and 4 scalars
+    DeviceArray<uint32_t> d_work;   // kMaxShards work counters, one per 64-B line
     bool work_dirty = true;         // not known to be zero
     uint32_t *d_lower = nullptr;    // kLowerRing flag words behind the work counters: speculative scans of un-normalised byte-path input (run_scan)
     uint32_t lower_idx = 0;
@@ -158,16 +165,15 @@ struct ntk_ctx {
     uint32_t pack_threads = 8;                       // NTK_OPT_COMPAT_PACK_THREADS
     uint64_t wait_poll_us = 50;                      // NTK_OPT_BATCH_WAIT_POLL_US (0: block in hipEventSynchronize)
     uint64_t gz_limit = 0, gz_window = 0, pipe_stats = 0;   // NTK_OPT_GZ_INMEM_LIMIT_BYTES / _STREAM_WINDOW_BYTES / NTK_OPT_PIPE_STATS: read by the producer (ntk_fastx_api.cpp) through ntk_ctx_get_option; 0 = its default
-    uint64_t *d_part_scalars = nullptr;
-    int part_blocks = 0;
-    uint16_t *d_lut = nullptr;  // four byte maps of 256 entries each, in the order of the accessors below
-    const uint16_t *lut_normalize() const { return d_lut; }
-    const uint16_t *lut_normalize_iupac() const { return d_lut + 256; }
-    const uint16_t *lut_strip() const { return d_lut + 512; }
-    const uint16_t *lut_complement() const { return d_lut + 768; }
-    Scratch scratch[6];
+    DeviceArray<uint16_t> d_lut;  // four byte maps of 256 entries each, in the order of the accessors below
+    const uint16_t *lut_normalize() const { return d_lut.p; }
+    const uint16_t *lut_normalize_iupac() const { return d_lut.p + 256; }
+    const uint16_t *lut_strip() const { return d_lut.p + 512; }
+    const uint16_t *lut_complement() const { return d_lut.p + 768; }
+    DeviceArray<uint8_t> scratch[6];   // of the per-sequence calls; each names its slots at the top of its body
+    template <class T> T *scratch_at(int slot) const { return (T *)scratch[slot].p; }
     CompatBank bank[kCompatBanks];   // the chunks the batched compat faces keep in flight (see run_banked)
-    void *h_pinned = nullptr;  // small pinned staging for scalar read-backs
+    Pinned<uint64_t> h_pinned;  // small pinned staging for scalar read-backs
     bool timing = false;
     std::vector<hipEvent_t> ev_free;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used;
@@ -182,10 +188,11 @@ struct ntk_ctx {
 };
 
 struct ntk_batch {
-    uint8_t *h_seq = nullptr;
-    uint64_t *h_off = nullptr;
-    uint8_t *d_seq = nullptr;
-    uint8_t *h_qual = nullptr, *d_qual = nullptr;  // allocated by the first ntk_batch_append_quality
+    Pinned<uint8_t> h_seq;
+    Pinned<uint64_t> h_off;
+    DeviceArray<uint8_t> d_seq;
+    Pinned<uint8_t> h_qual;                        // allocated by the first ntk_batch_append_quality ...
+    DeviceArray<uint8_t> d_qual;                   // ... and a batch without h_qual has no quality stream
     bool has_qual = false;                         // some record of the current fill carries qualities
     uint32_t qual_cutoff = 0;                      // ... appended for this cutoff (must be the one submitted)
     int device = 0;
@@ -196,27 +203,13 @@ struct ntk_batch {
 
 namespace {
 
-int ensure_scratch(ntk_ctx *c, int slot, size_t bytes)
-{
-    if (bytes < 256) bytes = 256;
-    Scratch &s = c->scratch[slot];
-    if (s.bytes >= bytes) return NTK_OK;
-    if (s.p) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(s.p)); s.p = nullptr; s.bytes = 0; }
-    size_t want = bytes + bytes / 4 + 4096;
-    HIPCHK(hipMalloc(&s.p, want));
-    s.bytes = want;
-    return NTK_OK;
-}
+// no scratch buffer is smaller than 256 bytes
+int ensure_scratch(ntk_ctx *c, int slot, size_t bytes) { return c->scratch[slot].ensure(c->stream, bytes < 256 ? 256 : bytes, grow_quarter_again_4k); }
 
 int ensure_partials(ntk_ctx *c, int blocks)
 {
-    if (c->part_blocks >= blocks) return NTK_OK;
-    if (c->d_part_hist) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->d_part_hist)); HIPCHK(hipFree(c->d_part_scalars)); }
-    c->d_part_hist = nullptr; c->d_part_scalars = nullptr; c->part_blocks = 0;
-    HIPCHK(hipMalloc(&c->d_part_hist, (size_t)blocks * kHistBins * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_part_scalars, (size_t)blocks * 4 * sizeof(uint64_t)));
-    c->part_blocks = blocks;
-    return NTK_OK;
+    const int rc = c->d_part_hist.ensure(c->stream, (uint64_t)blocks * kHistBins, grow_exact);
+    return rc ? rc : c->d_part_scalars.ensure(c->stream, (uint64_t)blocks * 4, grow_exact);
 }
 
 struct Mode { int kw; bool canon, tie_rc, accept_u; bool raw_bytes = false; };
@@ -370,8 +363,8 @@ struct Fold {
 };
 int launch_fold(ntk_ctx *c, int rows, const Fold &f = Fold())
 {
-    hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream, (const uint32_t *)c->d_part_hist,
-                       (const uint64_t *)c->d_part_scalars, rows, c->d_acc, f.rearm_shards ? c->d_work : (uint32_t *)nullptr, (int)f.rearm_shards,
+    hipLaunchKernelGGL(fold_kernel, dim3(kFoldBlocks), dim3(kFoldThreads), 0, c->stream, (const uint32_t *)c->d_part_hist.p,
+                       (const uint64_t *)c->d_part_scalars.p, rows, c->d_acc, f.rearm_shards ? c->d_work.p : (uint32_t *)nullptr, (int)f.rearm_shards,
                        f.alt_flag, f.alt_rows, f.undigested ? 1 : 0);
     HIPCHK(hipGetLastError());
     if (f.rearm_shards) c->work_dirty = false;
@@ -413,7 +406,7 @@ void launch_raw_bytes(ntk_ctx *c, bool wide, int blocks, const uint8_t *d_seq, u
     const uint32_t pb = k < 6 ? k : 6;
     launch_with_quality(c, wide ? bytes_reduce_q<true> : bytes_reduce_q<false>, wide ? &canonical_bytes_reduce_kernel<true> : &canonical_bytes_reduce_kernel<false>,
                         blocks, kPlThreads, d_qual, cutoff, d_seq, n, (n + 15) & ~(uint64_t)15, k, 2u * (k - pb), c->lut_complement(),
-                        c->d_part_hist, c->d_part_scalars, run_if, wide && normalized ? 1u : 0u);
+                        c->d_part_hist.p, c->d_part_scalars.p, run_if, wide && normalized ? 1u : 0u);
 }
 
 // The reduce routes of the byte path that no packed-value scan serves alone (d_qual with cutoff 1..255: the quality stream, masked before the
@@ -438,7 +431,7 @@ int run_bytes_reduce(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_par
         const FlagPair f = next_flag(c);
         launch_with_quality(c, normalized ? wide_reduce_q<true> : wide_reduce_q<false>,
                             normalized ? &wide_canonical_reduce_kernel<true> : &wide_canonical_reduce_kernel<false>, blocks, kWkThreads, d_qual, cutoff,
-                            d_seq, n, p->k, c->d_part_hist, c->d_part_scalars, f.flag, f.next);
+                            d_seq, n, p->k, c->d_part_hist.p, c->d_part_scalars.p, f.flag, f.next);
         HIPCHK(hipGetLastError());
         fold.alt_flag = f.flag; fold.alt_rows = blocks_raw;
     }
@@ -471,7 +464,7 @@ int launch_tile_scan(ntk_ctx *c, const TileScan &s, ScanArgs &a, bool zero_first
     const uint64_t n = a.n_bytes;
     const int blocks_raw = s.speculate ? raw_bytes_blocks(c, n) : 0;
     a.n_tiles = tile_count(n, s.stride);
-    a.work_counters = c->d_work;
+    a.work_counters = c->d_work.p;
     a.zero_words = NTK_ACC_WORDS;
     for (uint64_t tb = 0; tb < a.n_tiles; tb += kMaxTilesPerLaunch) {
         const LaunchPlan lp = plan_launch(n, s.stride, tb, blocks_max, waves_per_block, s.max_chunk);
@@ -485,11 +478,11 @@ int launch_tile_scan(ntk_ctx *c, const TileScan &s, ScanArgs &a, bool zero_first
         zero_first = false;
         // the work counters are zero on entry: the fold of the previous reduce scan re-armed them (launch_fold); anything else
         // (first use, a materialise scan, an error on the way) leaves work_dirty set and costs a memset here
-        if (c->work_dirty) HIPCHK(hipMemsetAsync(c->d_work, 0, kMaxShards * 64, c->stream));
+        if (c->work_dirty) HIPCHK(hipMemsetAsync(c->d_work.p, 0, kMaxShards * 64, c->stream));
         c->work_dirty = true;
         if (s.reduce) {
             if ((rc = ensure_partials(c, blocks > blocks_raw ? blocks : blocks_raw))) return rc;
-            a.part_hist = c->d_part_hist; a.part_scalars = c->d_part_scalars;
+            a.part_hist = c->d_part_hist.p; a.part_scalars = c->d_part_scalars.p;
         }
         Fold fold;
         fold.rearm_shards = a.n_shards;
@@ -620,11 +613,8 @@ int run_min_scan(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_params 
 
 void destroy_batch(ntk_batch *b)
 {
-    if (b->h_seq) (void)hipHostFree(b->h_seq);
-    if (b->h_off) (void)hipHostFree(b->h_off);
-    if (b->d_seq) (void)hipFree(b->d_seq);
-    if (b->h_qual) (void)hipHostFree(b->h_qual);
-    if (b->d_qual) (void)hipFree(b->d_qual);
+    b->h_seq.release(); b->h_off.release(); b->d_seq.release();
+    b->h_qual.release(); b->d_qual.release();
     if (b->ev_copied) (void)hipEventDestroy(b->ev_copied);
     if (b->ev_done) (void)hipEventDestroy(b->ev_done);
     delete b;
@@ -660,20 +650,20 @@ int init_ctx(ntk_ctx *c, void *stream, bool borrow)
     HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&c->down_stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc(&c->d_acc_own, NTK_ACC_WORDS * sizeof(uint64_t)));
-    c->d_acc = c->d_acc_own;
+    int rc;
+    if ((rc = c->d_acc_own.ensure(c->stream, NTK_ACC_WORDS, grow_exact))) return rc;
+    c->d_acc = c->d_acc_own.p;
     HIPCHK(hipMemsetAsync(c->d_acc, 0, NTK_ACC_WORDS * sizeof(uint64_t), c->stream));
-    HIPCHK(hipMalloc(&c->d_work, kMaxShards * 64 + kLowerRing * sizeof(uint32_t)));
-    c->d_lower = c->d_work + kMaxShards * 16;
+    if ((rc = c->d_work.ensure(c->stream, kMaxShards * 16 + kLowerRing, grow_exact))) return rc;
+    c->d_lower = c->d_work.p + kMaxShards * 16;
     HIPCHK(hipMemsetAsync(c->d_lower, 0, kLowerRing * sizeof(uint32_t), c->stream));
-    HIPCHK(hipMalloc(&c->d_lut, 4 * 256 * sizeof(uint16_t)));
-    HIPCHK(hipHostMalloc(&c->h_pinned, 64 * 1024, hipHostMallocDefault));
-    uint16_t *h = (uint16_t *)c->h_pinned;
+    if ((rc = c->d_lut.ensure(c->stream, 4 * 256, grow_exact)) || (rc = c->h_pinned.alloc(64 * 1024 / sizeof(uint64_t)))) return rc;
+    uint16_t *h = (uint16_t *)c->h_pinned.p;
     build_normalize_lut(h, false);
     build_normalize_lut(h + 256, true);
     build_strip_lut(h + 512);
     build_complement_lut(h + 768);
-    HIPCHK(hipMemcpyAsync(c->d_lut, h, 4 * 256 * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_lut.p, h, 4 * 256 * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return NTK_OK;
 }
@@ -733,17 +723,13 @@ void ntk_ctx_destroy(ntk_ctx *c)
     for (auto e : c->ev_free) (void)hipEventDestroy(e);
     for (auto b : c->pool) destroy_batch(b);
     c->pool.clear();
-    for (auto &s : c->scratch) if (s.p) (void)hipFree(s.p);
-    if (c->d_part_hist) (void)hipFree(c->d_part_hist);
-    if (c->d_part_scalars) (void)hipFree(c->d_part_scalars);
-    if (c->d_acc_own) (void)hipFree(c->d_acc_own);
-    if (c->d_lut) (void)hipFree(c->d_lut);
-    if (c->d_work) (void)hipFree(c->d_work);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
+    for (auto &s : c->scratch) s.release();
+    c->d_part_hist.release(); c->d_part_scalars.release();
+    c->d_acc_own.release(); c->d_lut.release(); c->d_work.release();
+    c->h_pinned.release();
     for (CompatBank &b : c->bank) {
-        if (b.h_stage) (void)hipHostFree(b.h_stage);
-        if (b.h_total) (void)hipHostFree(b.h_total);
-        for (auto &s : b.d) if (s.p) (void)hipFree(s.p);
+        b.h_stage.release(); b.h_total.release();
+        for (auto &s : b.d) s.release();
         for (hipEvent_t e : {b.ev_ready, b.ev_computed, b.ev_landed}) if (e) (void)hipEventDestroy(e);
     }
     if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -885,10 +871,10 @@ int ntk_reduce_device(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, const ntk_pa
 int ntk_accum_read(ntk_ctx *c, ntk_result *out)
 {
     if (!c || !out) return NTK_ERR_BAD_ARG;
-    uint64_t *h = (uint64_t *)c->h_pinned;
+    const uint64_t *h = c->h_pinned.p;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(h, c->d_acc, NTK_ACC_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    const int rc = c->h_pinned.read(c->stream, c->d_acc, NTK_ACC_WORDS);
+    if (rc) return rc;
     out->n_total = h[NTK_ACC_N_TOTAL]; out->n_fwd = h[NTK_ACC_N_FWD]; out->n_rc = h[NTK_ACC_N_RC];
     out->sum = h[NTK_ACC_SUM]; out->xr = h[NTK_ACC_XOR];
     memcpy(out->hist, h + NTK_ACC_HIST, sizeof(out->hist));
@@ -906,7 +892,7 @@ int ntk_accum_device_ptr(ntk_ctx *c, uint64_t **d_words)
 int ntk_accum_bind_device(ntk_ctx *c, uint64_t *d_words)
 {
     if (!c || ((uintptr_t)d_words & 7)) return NTK_ERR_BAD_ARG;
-    c->d_acc = d_words ? d_words : c->d_acc_own;
+    c->d_acc = d_words ? d_words : c->d_acc_own.p;
     return NTK_OK;
 }
 
@@ -951,16 +937,16 @@ int ntk_batch_acquire(ntk_ctx *c, uint64_t max_bytes, uint64_t max_records, ntk_
     if (!b) return NTK_ERR_NOMEM;
     b->cap_bytes = want_bytes;
     b->cap_records = want_records;
-    if (hipHostMalloc((void **)&b->h_seq, b->cap_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&b->h_off, (b->cap_records + 1) * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **)&b->d_seq, b->cap_bytes) != hipSuccess ||
-        hipEventCreateWithFlags(&b->ev_copied, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming) != hipSuccess) {
-        g_last_hip = (int)hipGetLastError();
-        destroy_batch(b);
-        return NTK_ERR_HIP;
-    }
-    b->h_off[0] = 0;
+    const auto create = [&]() -> int {   // (a fresh array synchronises no stream)
+        int rc;
+        if ((rc = b->h_seq.alloc(b->cap_bytes)) || (rc = b->h_off.alloc(b->cap_records + 1)) || (rc = b->d_seq.ensure(c->stream, b->cap_bytes, grow_exact))) return rc;
+        HIPCHK(hipEventCreateWithFlags(&b->ev_copied, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
+        return NTK_OK;
+    };
+    const int rc = create();
+    if (rc) { destroy_batch(b); return rc; }   // (skips what is null)
+    b->h_off.p[0] = 0;
     b->device = c->device;
     *out = b;
     return NTK_OK;
@@ -970,20 +956,17 @@ static int batch_append_impl(ntk_batch *b, const uint8_t *seq, const uint8_t *qu
 {
     if (!b || (!seq && n) || pre > NTK_PRE_NORMALIZE_IUPAC || b->in_flight) return NTK_ERR_BAD_ARG;
     if (b->n_records >= b->cap_records || b->n_bytes + n + 1 > b->cap_bytes) return NTK_ERR_CAPACITY;
-    if (qual && !b->h_qual) {
+    if (qual && !b->h_qual.p) {
         // quality stream: same capacity and offsets as the sequence stream; records appended without qualities read
-        // as 0xFF (never below a cutoff)
+        // as 0xFF (never below a cutoff).  The device array first: whichever allocation fails, h_qual stays empty and the batch usable
+        // without qualities (d_qual is empty or of this size: no stream is synchronised)
         HIPCHK(hipSetDevice(b->device));
-        HIPCHK(hipHostMalloc((void **)&b->h_qual, b->cap_bytes, hipHostMallocDefault));
-        if (hipMalloc((void **)&b->d_qual, b->cap_bytes) != hipSuccess) {
-            g_last_hip = (int)hipGetLastError();
-            (void)hipHostFree(b->h_qual); b->h_qual = nullptr;
-            return NTK_ERR_HIP;
-        }
-        memset(b->h_qual, 0xFF, b->n_bytes);
+        int rc = b->d_qual.ensure(nullptr, b->cap_bytes, grow_exact);
+        if (rc || (rc = b->h_qual.alloc(b->cap_bytes))) return rc;
+        memset(b->h_qual.p, 0xFF, b->n_bytes);
     }
-    uint8_t *o = b->h_seq + b->n_bytes;
-    uint8_t *oq = b->h_qual ? b->h_qual + b->n_bytes : nullptr;
+    uint8_t *o = b->h_seq.p + b->n_bytes;
+    uint8_t *oq = b->h_qual.p ? b->h_qual.p + b->n_bytes : nullptr;
     uint64_t w = 0;
     // the pre-step's deleted class is dropped here together with its quality byte - unless that quality is below the
     // cutoff: the reference masks (base, quality) pairs BEFORE normalize deletes anything (src/sequence.rs:285-296), so
@@ -1038,7 +1021,7 @@ static int batch_append_impl(ntk_batch *b, const uint8_t *seq, const uint8_t *qu
     o[w++] = '\n';
     b->n_bytes += w;
     b->n_records += 1;
-    b->h_off[b->n_records] = b->n_bytes;
+    b->h_off.p[b->n_records] = b->n_bytes;
     if (qual) { b->has_qual = true; b->qual_cutoff = cutoff; }
     return NTK_OK;
 }
@@ -1058,8 +1041,8 @@ int ntk_batch_append_quality(ntk_batch *b, const uint8_t *seq, const uint8_t *qu
 int ntk_batch_buffers(ntk_batch *b, uint8_t **seq, uint64_t **offsets, uint64_t *n_bytes, uint64_t *n_records)
 {
     if (!b) return NTK_ERR_BAD_ARG;
-    if (seq) *seq = b->h_seq;
-    if (offsets) *offsets = b->h_off;
+    if (seq) *seq = b->h_seq.p;
+    if (offsets) *offsets = b->h_off.p;
     if (n_bytes) *n_bytes = b->n_bytes;
     if (n_records) *n_records = b->n_records;
     return NTK_OK;
@@ -1074,21 +1057,21 @@ int ntk_batch_submit(ntk_ctx *c, ntk_batch *b, const ntk_params *p)
     HIPCHK(hipSetDevice(c->device));
     if (b->n_bytes) {
         const uint64_t padded = (b->n_bytes + 15) & ~(uint64_t)15;
-        for (uint64_t i = b->n_bytes; i < padded; i++) b->h_seq[i] = '\n';
+        for (uint64_t i = b->n_bytes; i < padded; i++) b->h_seq.p[i] = '\n';
         hipStream_t cs = (c->copy_streams > 1 && (c->copy_rr++ & 1u)) ? c->copy_stream2 : c->copy_stream;
-        HIPCHK(hipMemcpyAsync(b->d_seq, b->h_seq, padded, hipMemcpyHostToDevice, cs));
+        HIPCHK(hipMemcpyAsync(b->d_seq.p, b->h_seq.p, padded, hipMemcpyHostToDevice, cs));
         // the quality stream travels only when a cutoff is set and some record of this fill carries qualities
         const uint8_t *d_qual = nullptr;
         if (b->has_qual && quality_cutoff(p) != b->qual_cutoff) return NTK_ERR_BAD_ARG;
         if (quality_cutoff(p) && b->has_qual) {
-            for (uint64_t i = b->n_bytes; i < padded; i++) b->h_qual[i] = 0xFF;
-            HIPCHK(hipMemcpyAsync(b->d_qual, b->h_qual, padded, hipMemcpyHostToDevice, cs));
-            d_qual = b->d_qual;
+            for (uint64_t i = b->n_bytes; i < padded; i++) b->h_qual.p[i] = 0xFF;
+            HIPCHK(hipMemcpyAsync(b->d_qual.p, b->h_qual.p, padded, hipMemcpyHostToDevice, cs));
+            d_qual = b->d_qual.p;
         }
         HIPCHK(hipEventRecord(b->ev_copied, cs));
         HIPCHK(hipStreamWaitEvent(c->stream, b->ev_copied, 0));
-        rc = (p->flags & 0xFFu) ? minimizers_reduce_impl(c, b->d_seq, d_qual, b->n_bytes, p, p->flags & 0xFFu)
-                               : run_scan(c, b->d_seq, b->n_bytes, p, m, true, nullptr, nullptr, nullptr, d_qual);
+        rc = (p->flags & 0xFFu) ? minimizers_reduce_impl(c, b->d_seq.p, d_qual, b->n_bytes, p, p->flags & 0xFFu)
+                               : run_scan(c, b->d_seq.p, b->n_bytes, p, m, true, nullptr, nullptr, nullptr, d_qual);
         if (rc) return rc;
     }
     else if (p->flags & NTK_FLAG_RESET) HIPCHK(hipMemsetAsync(c->d_acc, 0, NTK_ACC_WORDS * sizeof(uint64_t), c->stream));
@@ -1116,7 +1099,7 @@ int ntk_batch_wait(ntk_ctx *c, ntk_batch *b)
         } else HIPCHK(hipEventSynchronize(b->ev_done));
         b->in_flight = false;
     }
-    b->n_bytes = 0; b->n_records = 0; b->h_off[0] = 0; b->has_qual = false;
+    b->n_bytes = 0; b->n_records = 0; b->h_off.p[0] = 0; b->has_qual = false;
     return NTK_OK;
 }
 
@@ -1126,10 +1109,10 @@ void ntk_batch_release(ntk_ctx *c, ntk_batch *b)
     if (c) (void)hipSetDevice(c->device);
     if (b->in_flight && b->ev_done) (void)hipEventSynchronize(b->ev_done);
     b->in_flight = false;
-    if (c && b->h_seq && b->h_off && b->d_seq) {  // keep it for the next acquire (bounded: 256 batches / 8 GiB pinned)
+    if (c && b->h_seq.p && b->h_off.p && b->d_seq.p) {  // keep it for the next acquire (bounded: 256 batches / 8 GiB pinned)
         std::lock_guard<std::mutex> g(c->pool_mu);
         if (c->pool.size() < 256 && c->pool_bytes + b->cap_bytes <= ((uint64_t)8 << 30)) {
-            b->n_bytes = 0; b->n_records = 0; b->h_off[0] = 0; b->has_qual = false; b->qual_cutoff = 0;
+            b->n_bytes = 0; b->n_records = 0; b->h_off.p[0] = 0; b->has_qual = false; b->qual_cutoff = 0;
             c->pool.push_back(b);
             c->pool_bytes += b->cap_bytes;
             return;
@@ -1148,14 +1131,13 @@ static int compact_with_lut(ntk_ctx *c, const uint8_t *seq, uint64_t n, const ui
     if (n == 0) return NTK_OK;
     HIPCHK(hipSetDevice(c->device));
     const uint32_t nblocks = (uint32_t)((n + kCompactBlockBytes - 1) / kCompactBlockBytes);
+    enum { kIn, kOut, kKept, kOffsets };   // scratch slots: input, output, kept per block, offsets + total + flags
     int rc;
-    if ((rc = ensure_scratch(c, 0, n))) return rc;                                   // input
-    if ((rc = ensure_scratch(c, 1, n))) return rc;                                   // output
-    if ((rc = ensure_scratch(c, 2, (size_t)nblocks * 4 + 16))) return rc;            // kept per block
-    if ((rc = ensure_scratch(c, 3, (size_t)nblocks * 8 + 64))) return rc;            // offsets + total + flags
-    uint8_t *d_in = (uint8_t *)c->scratch[0].p, *d_out = (uint8_t *)c->scratch[1].p;
-    uint32_t *d_kept = (uint32_t *)c->scratch[2].p;
-    uint64_t *d_off = (uint64_t *)c->scratch[3].p;
+    if ((rc = ensure_scratch(c, kIn, n)) || (rc = ensure_scratch(c, kOut, n))) return rc;
+    if ((rc = ensure_scratch(c, kKept, (size_t)nblocks * 4 + 16)) || (rc = ensure_scratch(c, kOffsets, (size_t)nblocks * 8 + 64))) return rc;
+    uint8_t *d_in = c->scratch_at<uint8_t>(kIn), *d_out = c->scratch_at<uint8_t>(kOut);
+    uint32_t *d_kept = c->scratch_at<uint32_t>(kKept);
+    uint64_t *d_off = c->scratch_at<uint64_t>(kOffsets);
     uint64_t *d_total = d_off + nblocks;
     uint32_t *d_flags = (uint32_t *)(d_total + 1);
     HIPCHK(hipMemcpyAsync(d_in, seq, n, hipMemcpyHostToDevice, c->stream));
@@ -1164,9 +1146,8 @@ static int compact_with_lut(ntk_ctx *c, const uint8_t *seq, uint64_t n, const ui
     hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t *)d_kept, d_off, nblocks, d_total);
     hipLaunchKernelGGL(compact_write_kernel, dim3(nblocks), dim3(kCompactThreads), 0, c->stream, (const uint8_t *)d_in, n, d_lut, (const uint64_t *)d_off, d_out);
     HIPCHK(hipGetLastError());
-    uint64_t *h = (uint64_t *)c->h_pinned;
-    HIPCHK(hipMemcpyAsync(h, d_total, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t *h = c->h_pinned.p;
+    if ((rc = c->h_pinned.read(c->stream, d_total, 2))) return rc;   // the total, then the two flag words
     const uint64_t total = h[0];
     memcpy(flags_out, h + 1, 8);
     if (total) {
@@ -1202,10 +1183,10 @@ int ntk_reverse_complement(ntk_ctx *c, const uint8_t *seq, uint64_t n, uint8_t *
     if (!c || (!seq && n) || (!out && n)) return NTK_ERR_BAD_ARG;
     if (n == 0) return NTK_OK;
     HIPCHK(hipSetDevice(c->device));
+    enum { kIn, kOut };   // scratch slots
     int rc;
-    if ((rc = ensure_scratch(c, 0, n))) return rc;
-    if ((rc = ensure_scratch(c, 1, n))) return rc;
-    uint8_t *d_in = (uint8_t *)c->scratch[0].p, *d_out = (uint8_t *)c->scratch[1].p;
+    if ((rc = ensure_scratch(c, kIn, n)) || (rc = ensure_scratch(c, kOut, n))) return rc;
+    uint8_t *d_in = c->scratch_at<uint8_t>(kIn), *d_out = c->scratch_at<uint8_t>(kOut);
     HIPCHK(hipMemcpyAsync(d_in, seq, n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(map_reverse_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream,
                        (const uint8_t *)d_in, d_out, n, c->lut_complement());
@@ -1241,23 +1222,21 @@ void bank_trim(ntk_ctx *c, size_t keep = kBankKeepBytes)
 {
     for (CompatBank &b : c->bank) {
         size_t dev = 0;
-        for (const Scratch &s : b.d) dev += s.bytes;
-        if (dev > keep) for (Scratch &s : b.d) { if (s.p) (void)hipFree(s.p); s.p = nullptr; s.bytes = 0; }
-        if (b.h_stage_bytes > keep) { (void)hipHostFree(b.h_stage); b.h_stage = nullptr; b.h_stage_bytes = 0; }
+        for (const auto &s : b.d) dev += s.bytes();
+        if (dev > keep) for (auto &s : b.d) s.release();
+        if (b.h_stage.bytes() > keep) b.h_stage.release();
     }
 }
 
 int bank_scratch(ntk_ctx *c, CompatBank &b, BankSlot slot, size_t bytes)
 {
     if (bytes < 256) bytes = 256;
-    Scratch &s = b.d[slot];
-    if (s.bytes >= bytes) return NTK_OK;
-    // (only this bank's own earlier work can still use the buffer, and that was waited for before the bank was re-used)
-    if (s.p) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipStreamSynchronize(c->copy_stream)); HIPCHK(hipStreamSynchronize(c->down_stream)); HIPCHK(hipFree(s.p)); s.p = nullptr; s.bytes = 0; }
-    const size_t want = bytes + bytes / 4 + 4096;
-    HIPCHK(hipMalloc(&s.p, want));
-    s.bytes = want;
-    return NTK_OK;
+    DeviceArray<uint8_t> &s = b.d[slot];
+    // All three streams are idle before a bank's buffer is replaced: ensure() synchronises the compute stream ahead of the free, the copy
+    // and down streams go first here, on the growing path only.  (Only this bank's own earlier work can still use the buffer, and that
+    // was waited for before the bank was re-used.)
+    if (bytes > s.cap && s.p) { HIPCHK(hipStreamSynchronize(c->copy_stream)); HIPCHK(hipStreamSynchronize(c->down_stream)); }
+    return s.ensure(c->stream, bytes, grow_quarter_again_4k);
 }
 
 int bank_init(CompatBank &b)
@@ -1266,8 +1245,7 @@ int bank_init(CompatBank &b)
     HIPCHK(hipEventCreateWithFlags(&b.ev_ready, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&b.ev_computed, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&b.ev_landed, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc((void **)&b.h_total, 64, hipHostMallocDefault));
-    return NTK_OK;
+    return b.h_total.alloc(8);   // (a 64-byte line)
 }
 
 int stream_sync(hipStream_t s) { HIPCHK(hipStreamSynchronize(s)); return NTK_OK; }
@@ -1334,13 +1312,9 @@ int compat_stage_a(ntk_ctx *c, CompatBank &b, const CompatJob &j, const CompatCu
     int rc;
     const uint64_t r0 = cut.r0, nrec = cut.nrec(), n = cut.bytes;
     const size_t stage_bytes = (size_t)n + (size_t)(nrec + 1) * 8 + 64;
-    if (b.h_stage_bytes < stage_bytes) {
-        if (b.h_stage) { HIPCHK(hipHostFree(b.h_stage)); b.h_stage = nullptr; b.h_stage_bytes = 0; }
-        HIPCHK(hipHostMalloc(&b.h_stage, stage_bytes + stage_bytes / 4, hipHostMallocDefault));
-        b.h_stage_bytes = stage_bytes + stage_bytes / 4;
-    }
-    uint64_t *h_start = (uint64_t *)b.h_stage;                       // 8-byte aligned head
-    uint8_t *h_seq = (uint8_t *)b.h_stage + (size_t)(nrec + 1) * 8;
+    if ((rc = b.h_stage.ensure(stage_bytes, grow_quarter_again))) return rc;   // (the bank is free: nothing of it is in flight)
+    uint64_t *h_start = (uint64_t *)b.h_stage.p;                     // 8-byte aligned head
+    uint8_t *h_seq = b.h_stage.p + (size_t)(nrec + 1) * 8;
     // record r of the chunk lands at offsets[r0 + r] - offsets[r0] + r (one break byte after every record before it): the
     // packing splits over threads without a prefix pass (one core packs ~5 GB/s of 150-byte records - less than the PCIe link
     // takes back - so a chunk is packed by up to ntk_ctx::pack_threads threads, default 8)
@@ -1404,7 +1378,7 @@ int compat_stage_a(ntk_ctx *c, CompatBank &b, const CompatJob &j, const CompatCu
     hipLaunchKernelGGL(cp_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t *)base, (uint64_t *)(base + b.o_off), b.nblocks,
                        (uint64_t *)(base + b.o_total));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b.h_total, base + b.o_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(b.h_total.p, base + b.o_total, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipEventRecord(b.ev_ready, c->stream));
     return NTK_OK;
 }
@@ -1414,7 +1388,7 @@ int compat_stage_b(ntk_ctx *c, CompatBank &b, const CompatJob &j, uint64_t *base
 {
     int rc;
     HIPCHK(hipEventSynchronize(b.ev_ready));
-    const uint64_t m = *b.h_total, at = *base_items;
+    const uint64_t m = *b.h_total.p, at = *base_items;
     const uint64_t take = at >= j.cap ? 0 : (m < j.cap - at ? m : j.cap - at);
     const bool values = j.kind != 0;
     if ((rc = bank_scratch(c, b, kSlotDense, (size_t)take * (8 + (values ? 8 : 0) + 1) + 64))) return rc;
@@ -1520,7 +1494,7 @@ int compat_planes(ntk_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint6
             hipLaunchKernelGGL(bit_kmers_planes_kernel<false>, grid, dim3(kPlThreads), 0, c->stream, d_bytes, nb, nt + 16, k,
                                (const uint32_t *)d_starts, sb_words, d_v16, d_r16, d_values, d_total);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(b.h_total, d_total, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(b.h_total.p, d_total, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipEventRecord(b.ev_computed, c->stream));
         HIPCHK(hipStreamWaitEvent(c->down_stream, b.ev_computed, 0));
         HIPCHK(hipMemcpyAsync(valid16 + b.wbase, d_v16, (size_t)nw * 2, hipMemcpyDeviceToHost, c->down_stream));
@@ -1531,7 +1505,7 @@ int compat_planes(ntk_ctx *c, const uint8_t *seq, const uint64_t *offsets, uint6
         return NTK_OK;
     };
     // a chunk that has fully landed: its item total joins the sum
-    const int rc = run_banked(c, offsets, n_records, 0, true, upload, compute_and_download, [&](CompatBank &b) { items += *b.h_total; });
+    const int rc = run_banked(c, offsets, n_records, 0, true, upload, compute_and_download, [&](CompatBank &b) { items += *b.h_total.p; });
     rec_bit[n_records] = words * 16;
     if (rc != NTK_OK) return rc;
     *total = items;
@@ -1667,7 +1641,7 @@ int ntk_ctx_trim(ntk_ctx *c)
     HIPCHK(hipStreamSynchronize(c->copy_stream));
     HIPCHK(hipStreamSynchronize(c->down_stream));
     bank_trim(c, 0);
-    for (Scratch &s : c->scratch) { if (s.p) (void)hipFree(s.p); s.p = nullptr; s.bytes = 0; }
+    for (auto &s : c->scratch) s.release();
     return NTK_OK;
 }
 
@@ -1683,6 +1657,7 @@ int ntk_minimizers_reduce_device(ntk_ctx *c, const uint8_t *d_seq, uint64_t n, c
 static int minimizers_reduce_impl(ntk_ctx *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n, const ntk_params *p, uint32_t w)
 {
     if (!c || w < 1 || w > 256) return NTK_ERR_BAD_ARG;
+    enum { kValues = 3, kValid = 4, kRc = 5 };   // scratch slots of the two-pass route: a value per position and the two planes
     Mode m;
     int rc = resolve_mode(p, true, &m);
     if (rc) return rc;
@@ -1713,25 +1688,23 @@ static int minimizers_reduce_impl(ntk_ctx *c, const uint8_t *d_seq, const uint8_
         const uint64_t c1 = c0 + chunk < n ? c0 + chunk : n;
         const uint64_t start = c0 > back ? (c0 - back) & ~(uint64_t)15 : 0;
         const uint64_t n_sub = c1 - start, nt = (n_sub + 15) / 16 * 16;
-        if ((rc = ensure_scratch(c, 3, nt * 8))) return rc;
-        if ((rc = ensure_scratch(c, 4, nt / 8 + 16))) return rc;
-        if ((rc = ensure_scratch(c, 5, nt / 8 + 16))) return rc;
-        uint64_t *d_val = (uint64_t *)c->scratch[3].p;
-        uint16_t *d_v16 = (uint16_t *)c->scratch[4].p, *d_r16 = (uint16_t *)c->scratch[5].p;
+        if ((rc = ensure_scratch(c, kValues, nt * 8)) || (rc = ensure_scratch(c, kValid, nt / 8 + 16)) || (rc = ensure_scratch(c, kRc, nt / 8 + 16))) return rc;
+        uint64_t *d_val = c->scratch_at<uint64_t>(kValues);
+        uint16_t *d_v16 = c->scratch_at<uint16_t>(kValid), *d_r16 = c->scratch_at<uint16_t>(kRc);
         if ((rc = run_scan(c, d_seq + start, n_sub, p, m, false, d_val, d_v16, d_r16, d_qual ? d_qual + start : nullptr))) return rc;
 #define NTK_WM(WW)                                                                                                    \
     case WW:                                                                                                          \
         hipLaunchKernelGGL(window_min_reduce_kernel<WW>, dim3(blocks), dim3(kWmThreads), 0, c->stream, (const uint64_t *)d_val, \
-                           (const uint16_t *)d_v16, (const uint16_t *)d_r16, n_sub, w, a.bin_shift, c->d_part_hist,    \
-                           c->d_part_scalars, c0 - start);                                                            \
+                           (const uint16_t *)d_v16, (const uint16_t *)d_r16, n_sub, w, a.bin_shift, c->d_part_hist.p,  \
+                           c->d_part_scalars.p, c0 - start);                                                          \
         break;
         switch (w <= 16 ? w : 0u) {   // compile-time windows up to 16 (register van Herk), the run-time walk otherwise
             NTK_WM(2) NTK_WM(3) NTK_WM(4) NTK_WM(5) NTK_WM(6) NTK_WM(7) NTK_WM(8) NTK_WM(9) NTK_WM(10) NTK_WM(11) NTK_WM(12)
             NTK_WM(13) NTK_WM(14) NTK_WM(15) NTK_WM(16)
         default:
             hipLaunchKernelGGL(window_min_reduce_kernel<0>, dim3(blocks), dim3(kWmThreads), 0, c->stream, (const uint64_t *)d_val,
-                               (const uint16_t *)d_v16, (const uint16_t *)d_r16, n_sub, w, a.bin_shift, c->d_part_hist,
-                               c->d_part_scalars, c0 - start);
+                               (const uint16_t *)d_v16, (const uint16_t *)d_r16, n_sub, w, a.bin_shift, c->d_part_hist.p,
+                               c->d_part_scalars.p, c0 - start);
         }
 #undef NTK_WM
         if ((rc = launch_fold(c, blocks))) return rc;   // (no work counters to re-arm: the materialise scan left them dirty)
@@ -1743,10 +1716,10 @@ int ntk_minimizer(ntk_ctx *c, const uint8_t *seq, uint64_t n, uint32_t m, uint8_
 {
     if (!c || !seq || !out || m < 1 || n < m) return NTK_ERR_BAD_ARG;  // the reference panics on n < m (sequence.rs:141)
     HIPCHK(hipSetDevice(c->device));
+    enum { kIn, kOut };   // scratch slots; kOut: the m bytes, then (16-byte aligned) the `best` word
     int rc;
-    if ((rc = ensure_scratch(c, 0, n))) return rc;
-    if ((rc = ensure_scratch(c, 1, (size_t)m + 64))) return rc;
-    uint8_t *d_in = (uint8_t *)c->scratch[0].p, *d_out = (uint8_t *)c->scratch[1].p;
+    if ((rc = ensure_scratch(c, kIn, n)) || (rc = ensure_scratch(c, kOut, (size_t)m + 64))) return rc;
+    uint8_t *d_in = c->scratch_at<uint8_t>(kIn), *d_out = c->scratch_at<uint8_t>(kOut);
     uint64_t *d_best = (uint64_t *)(d_out + ((m + 15) & ~15u));
     HIPCHK(hipMemcpyAsync(d_in, seq, n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(minimizer_bytes_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint8_t *)d_in, n, m,
@@ -1797,10 +1770,10 @@ int ntk_bit_minimizers(ntk_ctx *c, const uint64_t *values, uint64_t n, uint32_t 
     if (k < 1 || k > 32 || m < 1 || m > k) return NTK_ERR_BAD_K;
     if (n == 0) return NTK_OK;
     HIPCHK(hipSetDevice(c->device));
+    enum { kIn, kOut };   // scratch slots
     int rc;
-    if ((rc = ensure_scratch(c, 0, n * 8))) return rc;
-    if ((rc = ensure_scratch(c, 1, n * 8))) return rc;
-    uint64_t *d_in = (uint64_t *)c->scratch[0].p, *d_out = (uint64_t *)c->scratch[1].p;
+    if ((rc = ensure_scratch(c, kIn, n * 8)) || (rc = ensure_scratch(c, kOut, n * 8))) return rc;
+    uint64_t *d_in = c->scratch_at<uint64_t>(kIn), *d_out = c->scratch_at<uint64_t>(kOut);
     HIPCHK(hipMemcpyAsync(d_in, values, n * 8, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(bit_minimizer_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const uint64_t *)d_in, n, k, m, d_out);
     HIPCHK(hipGetLastError());
@@ -1815,12 +1788,11 @@ int ntk_bit_canonical(ntk_ctx *c, const uint64_t *values, uint64_t n, uint32_t k
     if (k < 1 || k > 32) return NTK_ERR_BAD_K;
     if (n == 0) return NTK_OK;
     HIPCHK(hipSetDevice(c->device));
+    enum { kIn, kOut, kWasRc };   // scratch slots
     int rc;
-    if ((rc = ensure_scratch(c, 0, n * 8))) return rc;
-    if ((rc = ensure_scratch(c, 1, n * 8))) return rc;
-    if ((rc = ensure_scratch(c, 2, n))) return rc;
-    uint64_t *d_in = (uint64_t *)c->scratch[0].p, *d_out = (uint64_t *)c->scratch[1].p;
-    uint8_t *d_f = (uint8_t *)c->scratch[2].p;
+    if ((rc = ensure_scratch(c, kIn, n * 8)) || (rc = ensure_scratch(c, kOut, n * 8)) || (rc = ensure_scratch(c, kWasRc, n))) return rc;
+    uint64_t *d_in = c->scratch_at<uint64_t>(kIn), *d_out = c->scratch_at<uint64_t>(kOut);
+    uint8_t *d_f = c->scratch_at<uint8_t>(kWasRc);
     HIPCHK(hipMemcpyAsync(d_in, values, n * 8, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(bit_canonical_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const uint64_t *)d_in, n, k, canonical, d_out, d_f);
     HIPCHK(hipGetLastError());
@@ -1835,11 +1807,10 @@ int ntk_quality_mask(ntk_ctx *c, const uint8_t *seq, const uint8_t *qual, uint64
     if (!c || (n && (!seq || !qual || !out))) return NTK_ERR_BAD_ARG;
     if (n == 0) return NTK_OK;
     HIPCHK(hipSetDevice(c->device));
+    enum { kSeq, kQual, kOut };   // scratch slots
     int rc;
-    if ((rc = ensure_scratch(c, 0, n))) return rc;
-    if ((rc = ensure_scratch(c, 1, n))) return rc;
-    if ((rc = ensure_scratch(c, 2, n))) return rc;
-    uint8_t *d_s = (uint8_t *)c->scratch[0].p, *d_q = (uint8_t *)c->scratch[1].p, *d_o = (uint8_t *)c->scratch[2].p;
+    if ((rc = ensure_scratch(c, kSeq, n)) || (rc = ensure_scratch(c, kQual, n)) || (rc = ensure_scratch(c, kOut, n))) return rc;
+    uint8_t *d_s = c->scratch_at<uint8_t>(kSeq), *d_q = c->scratch_at<uint8_t>(kQual), *d_o = c->scratch_at<uint8_t>(kOut);
     HIPCHK(hipMemcpyAsync(d_s, seq, n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_q, qual, n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(quality_mask_kernel, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const uint8_t *)d_s, (const uint8_t *)d_q, n, score, d_o);

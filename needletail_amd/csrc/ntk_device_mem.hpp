@@ -1,7 +1,8 @@
-// How a handle of a consumer library owns memory (included by ntk_consumer.hpp, which defines CT_HIPCHK and alloc_status): a device
-// array grown on demand, a pinned stage with its two synchronising round trips, and rocPRIM's temporary storage.  The only place of the
-// consumer libraries that allocates or frees.  Everything is in an anonymous namespace like the rest of the scaffold.  DESIGN.md
-// section 16.
+// How a handle owns memory: a device array grown on demand, a pinned stage with its two synchronising round trips, and rocPRIM's
+// temporary storage.  Whoever includes it defines CT_HIPCHK and alloc_status first - ntk_consumer.hpp for the libraries on the core's
+// ABI, ntk_api.hip for the core, whose versions record the error for ntk_last_hip_error.  The only place under csrc/ that allocates or
+// frees (ntk_pinned_alloc hands its memory to the caller and is the exception).  Everything is in an anonymous namespace like the rest
+// of the scaffold.  DESIGN.md section 16.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,8 @@ int alloc_status(hipError_t e);
 using Growth = uint64_t (*)(uint64_t have, uint64_t need);
 inline uint64_t grow_exact(uint64_t, uint64_t need) { return need; }
 inline uint64_t grow_half_again(uint64_t, uint64_t need) { return need + need / 2 + 64; }
+inline uint64_t grow_quarter_again(uint64_t, uint64_t need) { return need + need / 4; }                 // the core's pinned stage
+inline uint64_t grow_quarter_again_4k(uint64_t, uint64_t need) { return need + need / 4 + 4096; }       // the core's scratch and banks
 inline uint64_t grow_doubling(uint64_t have, uint64_t need)   // from 1024
 {
     uint64_t want = have ? have : 1024;
@@ -72,11 +75,14 @@ struct DeviceArray {
 template <class T>
 struct Pinned {
     T *p = nullptr;
+    uint64_t cap = 0;   // elements
+
+    uint64_t bytes() const { return cap * sizeof(T); }
 
     void release()
     {
         if (p) (void)hipHostFree(p);
-        p = nullptr;
+        p = nullptr; cap = 0;
     }
 
     // n elements, whatever it held before (the stream is idle)
@@ -85,8 +91,12 @@ struct Pinned {
         release();
         const hipError_t e = hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault);
         if (e != hipSuccess) { p = nullptr; return alloc_status(e); }
+        cap = n;
         return NTK_OK;
     }
+
+    // room for `need` elements (the stream is idle); a stage that is large enough costs no HIP call
+    int ensure(uint64_t need, Growth growth) { return need <= cap ? NTK_OK : alloc(growth(cap, need)); }
 
     // n device elements into the stage from element `at` on (synchronises)
     int read(hipStream_t stream, const T *d, uint64_t n, uint64_t at = 0)

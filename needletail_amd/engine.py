@@ -75,6 +75,9 @@ class Context:
     def synchronize(self):
         L.check(L.lib().ntk_ctx_synchronize(self._h), "ntk_ctx_synchronize")
 
+    def trim(self):
+        L.check(L.lib().ntk_ctx_trim(self._h), "ntk_ctx_trim")
+
     # -- reduce mode -----------------------------------------------------------------------------
     def accum_reset(self):
         L.check(L.lib().ntk_accum_reset(self._h), "ntk_accum_reset")

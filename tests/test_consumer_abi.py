@@ -75,6 +75,14 @@ def test_the_shared_pieces_are_used_and_not_defined_again(row):
         assert not re.search(r"hip(?:Host)?(?:Malloc|Free)\b", text), "the memory layer allocates"
 
 
+def test_the_core_takes_its_memory_from_the_same_layer():
+    """ntk_api.hip includes ntk_device_mem.hpp (with its own check macro and status) and defines none of its pieces again."""
+    api, mem = (open(os.path.join(L.CSRC, f)).read() for f in ("ntk_api.hip", L.CONSUMER_HPP[1]))
+    assert '#include "ntk_device_mem.hpp"' in api and "#define CT_HIPCHK" in api and re.search(r"\balloc_status\([^)]*\)\s*\{", api)
+    for pat in MEM_DEFS:
+        assert len(re.findall(pat, mem)) == 1 and not re.search(pat, api), pat
+
+
 CHECKS = ("check_exports", "check_header", "check_kernels", "check_product_files_never_name_the_checker", "check_no_device")
 
 

@@ -87,16 +87,24 @@ def test_the_shared_pieces_are_defined_once():
         assert f'#include "{want}"' in src, path
 
 
-def test_only_the_memory_layer_and_the_core_allocate():
-    """Device and pinned memory of the consumer libraries is allocated and freed in ntk_device_mem.hpp alone: apart from it, only the
-    core's own sources (ntk_api.hip, ntk_fastx*, ntk_pgzip*) name the four calls, comments included."""
-    core = re.compile(r"ntk_api\.hip$|ntk_fastx|ntk_pgzip")
-    found = set()
-    for name in sorted(os.listdir(CSRC)):
-        if re.search(r"\.(?:hip|hpp|cpp|h)$", name) and re.search(r"hip(?:Host)?(?:Malloc|Free)\b", open(os.path.join(CSRC, name)).read()):
-            found.add(name)
-    assert "ntk_device_mem.hpp" in found
-    assert [f for f in found if f != "ntk_device_mem.hpp" and not core.search(f)] == []
+def test_only_the_memory_layer_allocates():
+    """Device and pinned memory of the core and of the consumer libraries is allocated and freed in ntk_device_mem.hpp alone, comments
+    included: no other source under csrc/ names hipMalloc or hipFree, and the two pinned calls occur outside it once each, in
+    ntk_pinned_alloc / ntk_pinned_free of ntk_api.hip, which hand the memory to the caller.  The core's own buffer struct and the
+    separate capacity of its pinned stage are gone."""
+    sources = {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if re.search(r"\.(?:hip|hpp|cpp|h)$", name)}
+    found = {name for name, text in sources.items() if re.search(r"hip(?:Host)?(?:Malloc|Free)\b", text)}
+    assert found == {"ntk_device_mem.hpp", "ntk_api.hip"}
+    api = sources["ntk_api.hip"]
+    assert not re.search(r"hip(?:Malloc|Free)\b", api)
+    assert len(re.findall(r"hipHostMalloc\b", api)) == 1 and len(re.findall(r"hipHostFree\b", api)) == 1
+    assert re.search(r"int ntk_pinned_alloc\([^)]*\)\s*\{[^}]*hipHostMalloc\b[^}]*\}", api)
+    assert re.search(r"void ntk_pinned_free\([^)]*\)\s*\{[^}]*hipHostFree\b[^}]*\}", api)
+    assert '#include "ntk_device_mem.hpp"' in api
+    for pat in MEM_DEFS:
+        assert not re.search(pat, api), pat
+    for name, text in sources.items():
+        assert not re.search(r"struct Scratch\b|h_stage_bytes", text), name
 
 
 # ---- the host model of the table (tests/_count_model.py), which the edge tests aim with --------------------------------------

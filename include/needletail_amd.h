@@ -212,7 +212,7 @@ void ntk_comm_destroy(ntk_comm *comm);
  * packed-value scan, exact on mixed case); a quality stream (ntk_reduce_device_quality, batches that carry qualities) is masked in
  * on that route too, at any k; dense values (ntk_materialize_device) and windowed minimizers on such input are NTK_ERR_UNSUPPORTED
  * (NTK_ERR_BAD_K for k > 32) - normalize first. */
-int ntk_accum_reset(ntk_ctx *ctx);
+int ntk_accum_reset(ntk_ctx *ctx);                            /* async: the zeroing is queued on the ctx stream */
 int ntk_reduce_device(ntk_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, const ntk_params *p); /* async */
 /* Quality masking fused into the scan: `(seq, qual).quality_mask(cutoff)` (reference
  * src/sequence.rs:285-296: a base whose RAW quality byte is < cutoff becomes N) followed by the chain above, in one pass.
@@ -224,10 +224,11 @@ int ntk_reduce_device(ntk_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, cons
 int ntk_reduce_device_quality(ntk_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes,
                               const ntk_params *p);                                      /* async */
 int ntk_accum_read(ntk_ctx *ctx, ntk_result *out);            /* synchronises the ctx stream        */
-int ntk_accum_device_ptr(ntk_ctx *ctx, uint64_t **d_words);  /* NTK_ACC_WORDS u64 words on device  */
+int ntk_accum_device_ptr(ntk_ctx *ctx, uint64_t **d_words);  /* NTK_ACC_WORDS u64 words on device; host-side only: queues nothing and waits for nothing */
 /* Accumulate into caller-owned device memory (NTK_ACC_WORDS u64, e.g. a torch tensor that is then
  * all-reduced over RCCL); NULL re-binds the ctx's own buffer.  The caller zeroes / resets it via
- * ntk_accum_reset as usual. */
+ * ntk_accum_reset as usual.  Host-side only: queues nothing and waits for nothing - work already queued goes to the buffer that was
+ * bound when it was queued, later calls to the new one. */
 int ntk_accum_bind_device(ntk_ctx *ctx, uint64_t *d_words);
 
 /* ---- batch face, materialise mode -------------------------------------------------------------
@@ -240,7 +241,7 @@ int ntk_accum_bind_device(ntk_ctx *ctx, uint64_t *d_words);
 int ntk_materialize_device(ntk_ctx *ctx, const uint8_t *d_seq, uint64_t n_bytes, const ntk_params *p,
                            uint64_t *d_values, uint16_t *d_valid16, uint16_t *d_rc16);   /* async */
 int ntk_materialize_device_quality(ntk_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_bytes,
-                                   const ntk_params *p, uint64_t *d_values, uint16_t *d_valid16, uint16_t *d_rc16);
+                                   const ntk_params *p, uint64_t *d_values, uint16_t *d_valid16, uint16_t *d_rc16);   /* async */
 
 /* ---- batch face, pinned host batches (CPU parser fills, H2D copy overlaps the kernels) ---------
  * A batch exposes PINNED host memory; the caller (FastxReader loop) appends records between
@@ -440,11 +441,11 @@ int ntk_quality_mask(ntk_ctx *ctx, const uint8_t *seq, const uint8_t *qual, uint
 
 /* ---- device utilities (bench / parity properties; records stay resident in HBM) ----------------- */
 /* Synthetic read set of SURVEY.md §8d generated straight into HBM: reads first_read..+n_reads, each
- * read_len bases + '\n'; d_out holds n_reads*(read_len+1) bytes (+ padding to 16). */
+ * read_len bases + '\n'; d_out holds n_reads*(read_len+1) bytes (+ padding to 16).  Async on the ctx stream. */
 int ntk_synth_reads_device(ntk_ctx *ctx, uint64_t seed, uint64_t first_read, uint64_t n_reads,
                            uint32_t read_len, uint32_t n_per_1024, uint8_t *d_out);
 /* Reverse-complement every fixed-stride record in place order (record r = bytes [r*stride, r*stride+len)),
- * bytes outside records copied: the batch form of Sequence::reverse_complement. */
+ * bytes outside records copied: the batch form of Sequence::reverse_complement.  Async on the ctx stream. */
 int ntk_reverse_complement_records_device(ntk_ctx *ctx, const uint8_t *d_in, uint8_t *d_out,
                                           uint64_t n_records, uint32_t record_len, uint32_t stride);
 

@@ -1,4 +1,4 @@
-"""Every launch of the eleven k-mer libraries whose grid is capped by the device's CU count, one row each, and the GPU test that takes
+"""Every launch of the twelve k-mer libraries whose grid is capped by the device's CU count, one row each, and the GPU test that takes
 the kernel past one step of its grid-stride loop.
 
 A capped launch is `grid_for(items, per_block, n_cu * C)`: min(ceil(items / per_block), n_cu * C) blocks, each walking the items in
@@ -12,6 +12,8 @@ from typing import NamedTuple, Optional
 import _libraries as L
 
 COLORS_FILES = ("ntk_colors.hip", "ntk_colors_rule.hpp")
+ML_FILES = ("ntk_minimizer_list.hip", "ntk_ml_rule.hpp")
+ML_TESTS = "test_gpu_minimizer_list.py"
 NEW = "test_gpu_grid_steps.py"
 
 
@@ -19,16 +21,19 @@ def files_of(lib: str) -> tuple:
     """The csrc files that hold the library's launches: its source and its own headers."""
     if lib == "colors":
         return COLORS_FILES
+    if lib == "minimizer_list":
+        return ML_FILES
     return (f"ntk_{lib}.hip",) + tuple(L.BY_NAME[lib].headers)
 
 
-LIBS = tuple(row.name for row in L.LIBRARIES) + ("colors",)
+LIBS = tuple(row.name for row in L.LIBRARIES) + ("colors", "minimizer_list")
 
 # what the items of some rows are worth, for the arithmetic in the notes (tests/test_grid_steps.py ties them too)
 K_LANE_RUN = ("ntk_wide_walk.hpp", "kLaneRun", 64)         # bytes per run of the k > 32 walkers
 K_PER_LANE = (("ntk_sketch.hip", "kPerLane", 4), ("ntk_minhash.hip", "kPerLane", 4), ("ntk_record_minhash.hip", "kPerLane", 4))
 K_CHUNK = 64 << 20                                          # kChunkBases (tests/test_count_abi.py ties it)
 K_RMH_SEGMENT = 4 * 64 * 4 * 4                              # kSegment of ntk_record_minhash.hip: 4 * kTile * 4, kTile = 64 * kPerLane
+K_ML_TILE = ("ntk_ml_rule.hpp", "ML_TILE", 1024)            # window ends per tile of the two tile kernels of ntk_minimizer_list.hip
 
 
 class Row(NamedTuple):
@@ -173,6 +178,18 @@ ROWS = (
            (NEW, "test_colors_one_long_record_takes_a_second_step"), "262 144 window ends per step; one record of 327 680 valid windows"),
     _capped("colors", "kc_best_kernel", "records", "ntk_colors.hip", "n_records", 256, "kThreads", 8, "(unsigned)h->n_cu * 8",
             (NEW, "test_colors_best_of_one_window_records"), "524 288 records per step; 655 360 records of one window"),
+    # ---- minimizer_list: both tile kernels run once per chunk of 64 Mi bases -------------------------------------------------------------------
+    _capped("minimizer_list", "ml_select_kernel", "tiles of 1 024 window ends", "ntk_minimizer_list.hip", "tiles", 1, "1", 8, "resident",
+            (ML_TESTS, "test_tile_seams_of_the_select_kernel"),
+            "2 048 tiles = 2 Mi window ends per step, block b takes the tiles b, b + grid, ...; the seam batch is above two steps (sparse, "
+            "aimed k-mers), the exact one 1.25 steps of random reads with a quality stream, all five fields",
+            cap_def="const unsigned resident = (unsigned)m->n_cu * ML_BLOCKS_PER_CU;", also=(ML_TESTS, "test_exact_past_one_step_of_the_grid")),
+    _capped("minimizer_list", "ml_scatter_kernel", "tiles of 1 024 window ends", "ntk_minimizer_list.hip", "own_tiles", 1, "1", 8, "resident",
+            (ML_TESTS, "test_more_tiles_than_one_step_of_the_grid"),
+            "2 048 tiles per launch before a block takes a second one (a contiguous run of `per` tiles, no stride: the record starts are "
+            "walked along the run); 2.5 steps of random reads are runs of 3 tiles (a digest), the exact one 1.25 steps: runs of 2; "
+            "test_record_starts_carried_along_a_blocks_tiles has 2.25 steps, runs of 3 with skipped tiles and 5 000 equal starts inside them",
+            cap_def="const unsigned resident = (unsigned)m->n_cu * ML_BLOCKS_PER_CU;", also=(ML_TESTS, "test_exact_past_one_step_of_the_grid")),
 )
 
 

@@ -1,19 +1,19 @@
-"""A seeded, structured, differential fuzz of the eleven k-mer libraries (count table, wide count table, HyperLogLog sketch, read
+"""A seeded, structured, differential fuzz of the twelve k-mer libraries (count table, wide count table, HyperLogLog sketch, read
 abundance, read trimmer with its batch writer, MinHash; per-record MinHash, the sketch set, k-mer set algebra narrow and wide, the de
-Bruijn graph, the coloured index) against the host models the suite already has.  Shared by tests/test_lib_fuzz_inputs.py (CPU: the
+Bruijn graph, the coloured index; the minimizer lists) against the host models the suite already has.  Shared by tests/test_lib_fuzz_inputs.py (CPU: the
 slices are not vacuous), tests/test_gpu_lib_fuzz.py (the fixed slices) and tools/lib_fuzz.py (time-budgeted runs, replay, dump).
 Importable without a GPU: torch is imported only inside the device functions.
 
 Truth is the existing models only: `_count_helpers.oracle_values` / `oracle_items`, `test_gpu_wide_count.oracle_items`,
 `_sketch_model`, `_minhash_model`, `_abundance_model`, `_trim_model`, `_record_minhash_model`, `_mhset_model`, `_kmer_sets_model`,
-`_dbg_model`, `_colors_model`.  Every comparison is `array_equal` / `==`, the double columns of MinHashSet.compare included (as
+`_dbg_model`, `_colors_model`, `_minimizer_list_model`.  Every comparison is `array_equal` / `==`, the double columns of MinHashSet.compare included (as
 tests/test_gpu_minhash_set.py compares them: the counts are small, every sum is exact in a double).
 
 The generator (`make_case`).  Query records and a related reference set (the table's batch) are sampled from one random genome of a
 few kb with substitution errors, at different and uneven coverage, plus foreign reads and exact duplicates, so that abundances
 differ along a record.  Record content kinds are those of tools/gpu_fuzz.py's make_input (KINDS); record lengths come from EDGE
-lengths derived from the kernels' constants (`edge_lengths(k, stage)`: the six first stages share one dict, `colors` and
-`record_minhash` add their own).  The six first stages draw exactly what they drew before the newer five were added
+lengths derived from the kernels' constants (`edge_lengths(k, stage)`: the six first stages share one dict, `colors`,
+`record_minhash` and `minimizer_list` add their own).  The six first stages draw exactly what they drew before the newer five were added
 (tests/test_lib_fuzz_inputs.py pins a digest of each slice).
 
 The five newer stages.  `record_minhash`: per-record sketches of the batch, of a prefix and with the quality stream on one handle, the
@@ -24,6 +24,15 @@ reference set), compare, totals, every op and rule, one chained op on a result n
 set's k-mers (with one periodic read each of DBG_UNITS, two isolated cycles), and its unitig batch handed on, as device tensors, to a
 fresh count table, ReadAbundance and RecordMinHash.  `colors`: an index built colour by colour through tables, sets and per-key masks,
 the batch screened, and the trimmer's compacted device batch screened as it is.  The chains keep every buffer on the device.
+
+The `minimizer_list` stage (the twelfth library; its stage goes last, so the eleven before it draw what they drew).  (w, order) are drawn
+before the records (`draw_extra`): w from four classes (ML_W_CLASSES: 1, the powers of two, their neighbours - where a window is two
+overlapping ranges of the largest power of two below w -, typical ones), order LEX or HASH; the record lengths add the windows' own edges
+(k + w - 2 .. k + w: no, one, two windows; k + 2 w - 1: a run of w + 1) and records of ML_TILE - 1, ML_TILE, ML_TILE + 1 window ends.  The
+checker holds all five CSR fields of one handle to `_minimizer_list_model` without and with the quality stream, on a prefix of the records,
+the statistics, the result where it lies on the device, the digest to the core's windowed-minimizer reduce (canonical path, LEX), and a
+second, smaller batch on the same handle.  A case's batch is 6 .. 20 tiles of random, junk-bearing, masked content: what meets a tile
+boundary there is proved in tests/test_lib_fuzz_inputs.py, planted wrong rules included.
 
 Excluded inputs (what a header rules out is not generated for that stage):
   * bytes of the pre-step's "deleted" class inside a record - needletail_amd.h, "Device batch layout: ... no bytes of the pre-step's
@@ -56,6 +65,7 @@ import _dbg_model as DM
 import _kmer_sets_model as KS_
 import _mhset_model as SM
 import _minhash_model as M
+import _minimizer_list_model as MM
 import _record_minhash_model as RM
 import _sketch_model as S
 import _trim_model as T
@@ -63,7 +73,7 @@ from _count_helpers import M64, PATH_PRES, oracle_items, oracle_values, pack, qu
 
 BYTES, BITS, BITS_CANON = nt.PATH_BYTES_CANONICAL, nt.PATH_BITS, nt.PATH_BITS_CANONICAL
 OLD_STAGES = ("count", "count_wide", "minhash", "minhash_wide", "abundance", "trim")
-NEW_STAGES = ("record_minhash", "kmer_sets", "kmer_sets_wide", "dbg", "colors")
+NEW_STAGES = ("record_minhash", "kmer_sets", "kmer_sets_wide", "dbg", "colors", "minimizer_list")
 STAGES = OLD_STAGES + NEW_STAGES   # a stage's index seeds its cases: new stages go at the end
 WIDE_STAGES = ("count_wide", "minhash_wide", "kmer_sets_wide")
 KS = (1, 2, 3, 15, 16, 17, 21, 31, 32)
@@ -86,12 +96,15 @@ N_COLORS = (1, 2, 3, 8, 63, 64)
 ROUTES = ("table", "set", "masks")
 COMPARE_SIDE = 24                # MinHashSet.compare is held to the Python model on at most 24 x 24 pairs
 RMH_EDGE_MAX = 5000              # the num-dependent record lengths of the record_minhash stage stay at or below this many windows
+ML_TILE = MM.TILE                # ML_TILE of ntk_ml_rule.hpp: window ends per tile of ml_select_kernel and ml_scatter_kernel
+ML_W_CLASSES = {"one": (1,), "power_of_two": (2, 16, 64, 256), "neighbour": (3, 15, 17, 63, 65, 255), "typical": (5, 11, 19)}
+ML_ORDERS = (MM.LEX, MM.HASH)
 
 # the fixed slices of the GPU suite: stage -> (seed, cases).  tests/test_lib_fuzz_inputs.py proves on the CPU that each meets its
 # conditions; the counts are the smallest at which they do (seeds 100..139 were searched per stage)
 SLICES = {"count": (103, 3), "count_wide": (111, 3), "minhash": (134, 8), "minhash_wide": (131, 10), "abundance": (104, 3),
           "trim": (111, 4), "record_minhash": (113, 8), "kmer_sets": (117, 3), "kmer_sets_wide": (133, 2), "dbg": (127, 4),
-          "colors": (130, 4)}
+          "colors": (130, 4), "minimizer_list": (101, 15)}
 
 LANE_RUN = S.LANE_RUN            # kLaneRun (ntk_wide_count.hip, ntk_sketch.hip, ntk_wide_walk.hpp): window ends per lane
 LONG_PIECES_BYTES = 2048 * 16    # kLongPieces (ntk_trim.hip) 16-byte pieces: beyond it a record goes to rt_copy_long_kernel
@@ -112,9 +125,10 @@ def rmh_want(num: int) -> int:
     return 2 * num + 16          # rmh_want of ntk_rmh_rule.hpp
 
 
-def edge_lengths(k: int, stage: str = "count", num: int = 0) -> dict:
+def edge_lengths(k: int, stage: str = "count", num: int = 0, window: int = 0) -> dict:
     """name -> record length L, each from a constant of the kernels (w = candidate windows, L = w + k - 1).  The six first stages share
-    one dict; `colors` and `record_minhash` add what their own constants name (`num`: the bottom-s size of a record_minhash case)."""
+    one dict; `colors`, `record_minhash` and `minimizer_list` add what their own constants name (`num`: the bottom-s size of a
+    record_minhash case; `window`: the w of a minimizer_list case, k-mers per window)."""
     e = {
         "0": 0, "1": 1,                                       # the empty record (one break byte) and the shortest one
         "k-2": max(k - 2, 0), "k-1": k - 1,                   # no window
@@ -139,6 +153,12 @@ def edge_lengths(k: int, stage: str = "count", num: int = 0) -> dict:
             e[f"w{w}"] = w + k - 1
         for w in (127, 128, 129):  # two rounds
             e[f"w{w}"] = w + k - 1
+    if stage == "minimizer_list":
+        # no window, one, two, and a run of window + 1 windows (more than any span)
+        for name, L in (("k+w-2", k + window - 2), ("k+w-1", k + window - 1), ("k+w", k + window), ("k+2w-1", k + 2 * window - 1)):
+            e[name] = max(L, 0)
+        for w in (ML_TILE - 1, ML_TILE, ML_TILE + 1):   # ML_TILE of ntk_ml_rule.hpp: a tile of ml_select_kernel and ml_scatter_kernel
+            e[f"T{w}"] = w + k - 1
     if stage == "record_minhash":
         for w in (4095, 4096, 4097):   # kSegment of ntk_record_minhash.hip (kTile = 256 is w255 .. w257 above)
             e[f"w{w}"] = w + k - 1
@@ -157,7 +177,7 @@ ALL_LONG_CLASSES = LONG_CLASSES + (COLORS_LONG,)
 
 def long_classes(stage: str) -> tuple:
     """The long record classes a stage draws: the tables of kmer_sets and dbg take what `count` has covered."""
-    if stage in ("kmer_sets", "kmer_sets_wide", "dbg"):
+    if stage in ("kmer_sets", "kmer_sets_wide", "dbg", "minimizer_list"):   # (the minimizer list's 64 Mi seam stays with its own tests)
         return ()
     return ("long_pieces", COLORS_LONG) if stage == "colors" else LONG_CLASSES
 
@@ -209,7 +229,7 @@ class Case:
         return self.extra.get("kind", {}).get("num", 0)
 
     def edges(self) -> dict:
-        return edge_lengths(self.k, self.stage, self.num())
+        return edge_lengths(self.k, self.stage, self.num(), self.extra.get("w", 0))
 
     def tag(self) -> str:
         return f"k {self.k} path {self.path} pre {self.pre} cutoff {self.cutoff} records {len(self.records)} bytes {len(self.buf())}"
@@ -378,7 +398,12 @@ def draw_params(rng, stage):
 
 
 def draw_extra(rng, stage) -> dict:
-    """What a new stage fixes before its records are made: the sketch rule of a record_minhash case, whose num names edge lengths."""
+    """What a new stage fixes before its records are made: the sketch rule of a record_minhash case, whose num names edge lengths; the
+    window and the order of a minimizer_list case."""
+    if stage == "minimizer_list":
+        names = list(ML_W_CLASSES)
+        ws = ML_W_CLASSES[names[int(rng.integers(0, len(names)))]]
+        return dict(w=int(ws[int(rng.integers(0, len(ws)))]), order=int(ML_ORDERS[int(rng.integers(0, len(ML_ORDERS)))]))
     if stage != "record_minhash":
         return {}
     kind = dict(num=int(rng.choice(RMH_NUMS))) if rng.random() < 0.5 else dict(scaled=int(rng.choice(SCALEDS)))
@@ -618,6 +643,35 @@ def colors_steps(case, d):
 
 def colors_values(case, use_q: bool):
     return [KM.record_values(r, case.k, case.path, case.pre, case.quals[i] if use_q else None, case.cutoff) for i, r in enumerate(case.records)]
+
+
+def draw_ml(rng, case) -> dict:
+    """The checker's draws of a minimizer_list case (its window and order were drawn before the records: `draw_extra`)."""
+    n = len(case.records)
+    return dict(prefix=int(rng.integers(1, n + 1)), prefix_q=bool(rng.random() < 0.5), second_q=bool(rng.random() < 0.5),
+                second_budget=int(rng.integers(200, 3000)), trim=bool(rng.random() < 0.3))
+
+
+def ml_entries(case, use_q: bool, n_records=None):
+    """(the model's entries, offsets, n_bytes) of the case's first `n_records` records (None: all): the packed buffer cut at that
+    record's end, `_trim_model.offsets`, and the quality stream where `use_q`."""
+    off = case.offsets()
+    m = len(case.records) if n_records is None else n_records
+    n_bytes = int(off[m])
+    qual = case.qual_stream()[:n_bytes] if use_q else None
+    ent = MM.entries_of(case.buf()[:n_bytes], case.k, case.extra["w"], case.path, case.pre, case.extra["order"], qual, case.cutoff)
+    return ent, off[:m + 1], n_bytes
+
+
+def ml_want(case, use_q: bool, n_records=None):
+    """The CSR `MinimizerList.read()` is held to."""
+    ent, off, n_bytes = ml_entries(case, use_q, n_records)
+    return MM.csr(ent, off, n_bytes, case.k)
+
+
+def ml_second_case(rng, case, d) -> Case:
+    """The second, smaller batch of a minimizer_list case: the same parameters, window and order."""
+    return make_case(rng, case.k, case.path, case.pre, budget=d["second_budget"], allow_long=False, stage=case.stage, extra=case.extra)
 
 
 def trim_chain(case, items, setting):
@@ -1109,9 +1163,88 @@ def check_colors(sess, case, rng):
     return what
 
 
+ML_FIELDS = ("offsets", "pos", "values", "strand", "span")
+
+
+def _eq_ml(got, want, what):
+    for name, g, w in zip(ML_FIELDS, got, want):
+        _eq(np.asarray(g).astype(np.uint64), np.asarray(w).astype(np.uint64), f"{what} {name}")
+
+
+class _DeviceView:
+    """`n` words of `typestr` at a device address, for torch.as_tensor."""
+
+    def __init__(self, address, n, typestr):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (address, False), "version": 2}
+
+
+def _ml_device_result(ml, n_records):
+    """The held result cloned where it lies on the device, in the form of read()."""
+    import torch
+    d_off, d_pos, d_val, d_info, n = ml.device_arrays()
+    clone = lambda a, m, t: torch.as_tensor(_DeviceView(a, m, t), device="cuda").clone().cpu().numpy() if m else np.zeros(0, dtype=t)   # noqa: E731
+    info = clone(d_info, n, "<i4").view(np.uint32)
+    return (clone(d_off, n_records + 1, "<i8").view(np.uint64), clone(d_pos, n, "<i8").view(np.uint64), clone(d_val, n, "<i8").view(np.uint64),
+            (info & 1).astype(np.uint8), info >> 1)
+
+
+def _ml_core_digest(ctx, dev, n_bytes, k, w, path, pre):
+    """What the core's windowed-minimizer reduce folds on the same device buffer (w = 256 does not fit the flags of reduce_device)."""
+    ctx.accum_reset()
+    if w <= 255:
+        ctx.reduce_device(dev, n_bytes, k, path, pre, w=w)
+    else:
+        ctx.minimizers_reduce_device(dev, n_bytes, k, w, path, pre)
+    return ctx.accum_read()
+
+
+def check_minimizer_list(sess, case, rng):
+    """One handle per case: all five CSR fields without and with the quality stream, the statistics and the result on the device each
+    time; the digest against the core's (a canonical path in LEX order); a prefix of the records; then a second, smaller case, whose
+    result replaces the one held."""
+    k, path, pre, cutoff = case.k, case.path, case.pre, case.cutoff
+    w, order = case.extra["w"], case.extra["order"]
+    d = draw_ml(rng, case)
+    second = ml_second_case(rng, case, d)
+    what = f"minimizer_list w {w} order {order} {d}"
+    buf, off, n = case.buf(), case.offsets(), len(case.records)
+    dev, dq, d_off = upload(buf, fill=ord("A")), upload(case.qual_stream().tobytes(), fill=0xFF), _dev_u64(off)
+    q = dict(d_qual=dq, quality_cutoff=cutoff)
+
+    def held(ml, want, n_records, name):
+        _eq_ml(ml.read(), want, name)
+        st = ml.stats()
+        _eq([st["n_records"], st["n_entries"], st["n_windows"], st["n_chunks"]], [n_records, want[1].size, int(want[4].sum()), 1], name + " stats")
+        _eq_ml(_ml_device_result(ml, n_records), want, name + " on the device")
+
+    with nt.MinimizerList(k, path, w, order, sess.ctx) as ml:
+        for use_q in (False, True):
+            name = what + f" quality {use_q}"
+            want = ml_want(case, use_q)
+            ml.run_device(dev, len(buf), d_off, n, pre, **(q if use_q else {}))
+            held(ml, want, n, name)
+            if not use_q and order == MM.LEX and path != BITS:
+                got = ml.read()
+                core = _ml_core_digest(sess.ctx, dev, len(buf), k, w, path, pre)
+                if not MM.same_digest(MM.digest(got[2], got[3], got[4], k), core):
+                    raise Mismatch(name + " digest against the core's windowed-minimizer reduce")
+        m = d["prefix"]   # the bytes after the prefix are readable and are not input
+        ml.run_device(dev, int(off[m]), d_off, m, pre, **(q if d["prefix_q"] else {}))
+        held(ml, ml_want(case, d["prefix_q"], m), m, what + f" first {m} records")
+        if d["trim"]:
+            ml.trim()
+        buf2, n2 = second.buf(), len(second.records)
+        dev2, dq2 = upload(buf2, fill=ord("A")), upload(second.qual_stream().tobytes(), fill=0xFF)
+        kw = dict(d_qual=dq2, quality_cutoff=second.cutoff) if d["second_q"] else {}
+        ml.run_device(dev2, len(buf2), _dev_u64(second.offsets()), n2, pre, **kw)
+        held(ml, ml_want(second, d["second_q"]), n2, what + " the second, smaller case")
+    return what
+
+
 CHECKERS = {"count": check_count, "count_wide": check_count, "minhash": check_minhash, "minhash_wide": check_minhash,
             "abundance": check_abundance, "trim": check_trim, "record_minhash": check_record_minhash, "kmer_sets": check_kmer_sets,
-            "kmer_sets_wide": check_kmer_sets, "dbg": check_dbg, "colors": check_colors}
+            "kmer_sets_wide": check_kmer_sets, "dbg": check_dbg, "colors": check_colors,
+            "minimizer_list": check_minimizer_list}
 
 
 def run_case(sess, seed, stage, it):

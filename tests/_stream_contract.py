@@ -1,5 +1,5 @@
-"""The stream contract of the device face, call by call: one row per exported function of include/needletail_amd.h and the eleven
-include/needletail_amd_*.h that takes a device pointer or queues work on the context's stream.  tests/test_stream_contract.py holds the
+"""The stream contract of the device face, call by call: one row per exported function of include/needletail_amd.h, the eleven
+include/needletail_amd_*.h and include/needletail_amd/minimizer_list.h that takes a device pointer or queues work on the context's stream.  tests/test_stream_contract.py holds the
 rows to the headers; tests/test_gpu_stream_order.py holds the calls to the rows.
 
 A row's class is what the header promises about the context's stream:
@@ -10,8 +10,8 @@ A row's class is what the header promises about the context's stream:
   MAY_SYNC  the call may or may not wait for the stream; its result is ordered on the stream either way.
   SYNC      the stream is drained when the call returns: outputs are written, host results are final.
 `words` are the header's own, quoted; `where` says whether they stand at the declaration ("decl": in the comment in front of it or on its
-line) or in the comment at the head of the file, which then names the call ("head").  `test` is the GPU test of
-tests/test_gpu_stream_order.py that makes the call with work pending.
+line) or in the comment at the head of the file, which then names the call ("head").  `test` is the GPU test that makes the call with work
+pending: of tests/test_gpu_stream_order.py, or of the file the row names in `file`.
 
 Out of scope, in one line: the compat face (host arrays in, host arrays out; "eager, synchronous"), the readers and the whole-file
 pipelines, the option / timing / communicator calls, create / destroy / release, and ntk_batch_acquire / append / buffers / wait / release
@@ -27,13 +27,15 @@ GPU_TESTS = "test_gpu_stream_order.py"
 
 HEADERS = ("needletail_amd.h", "needletail_amd_count.h", "needletail_amd_wide_count.h", "needletail_amd_sketch.h", "needletail_amd_minhash.h",
            "needletail_amd_abundance.h", "needletail_amd_trim.h", "needletail_amd_record_minhash.h", "needletail_amd_minhash_set.h",
-           "needletail_amd_kmer_sets.h", "needletail_amd_dbg.h", "needletail_amd_colors.h")
+           "needletail_amd_kmer_sets.h", "needletail_amd_dbg.h", "needletail_amd_colors.h", "needletail_amd/minimizer_list.h")
 
-Row = collections.namedtuple("Row", "function cls header words where test")
+Row = collections.namedtuple("Row", "function cls header words where test file", defaults=(GPU_TESTS,))
 
-_CORE, _COUNT, _WIDE, _SKETCH, _MINHASH, _ABUND, _TRIM, _RMH, _MHSET, _KSETS, _DBG, _COLORS = HEADERS
+_CORE, _COUNT, _WIDE, _SKETCH, _MINHASH, _ABUND, _TRIM, _RMH, _MHSET, _KSETS, _DBG, _COLORS, _ML = HEADERS
 _TABLE_HEAD = "stats, extract, spectrum and lookup synchronise it"
 _KSETS_HEAD = "Every call returns a status code of needletail_amd.h and is synchronous on the context's stream"
+_ML_HEAD = "run_device, read, stats and trim are SYNCHRONOUS: they return when the work they queued on the context's stream is done"
+_ML_TESTS = "test_gpu_minimizer_list.py"
 
 
 def _table_rows(prefix, header):
@@ -101,6 +103,12 @@ ROWS = [
     Row("ntk_kmer_colors_stats", SYNC, _COLORS, "Synchronises", "decl", "test_kmer_colors_add"),
     Row("ntk_kmer_colors_lookup_device", SYNC, _COLORS, "Synchronous.", "decl", "test_kmer_colors_run_and_lookup"),
     Row("ntk_kmer_colors_run_device", SYNC, _COLORS, "Synchronous: the call returns after everything is written.", "decl", "test_kmer_colors_run_and_lookup"),
+    # the minimizer lists: the library's own GPU file makes the calls with work pending
+    Row("ntk_minimizer_list_run_device", SYNC, _ML, _ML_HEAD, "head", "test_stream_order", _ML_TESTS),
+    Row("ntk_minimizer_list_read", SYNC, _ML, _ML_HEAD, "head", "test_stream_order", _ML_TESTS),
+    Row("ntk_minimizer_list_result_device", ASYNC, _ML, "host-side only: queues nothing and waits for nothing", "decl", "test_stream_order", _ML_TESTS),
+    Row("ntk_minimizer_list_stats", SYNC, _ML, _ML_HEAD, "head", "test_stream_order", _ML_TESTS),
+    Row("ntk_minimizer_list_trim", SYNC, _ML, _ML_HEAD, "head", "test_stream_order", _ML_TESTS),
 ]
 
 # calls without a device pointer that the headers' contract sentences name: they queue work on the context's stream or wait for it
@@ -109,7 +117,16 @@ NAMED = ("ntk_accum_reset", "ntk_accum_read", "ntk_batch_submit",
          "ntk_kmer_sketch_reset", "ntk_kmer_sketch_registers", "ntk_kmer_sketch_merge", "ntk_kmer_sketch_estimate",
          "ntk_minhash_reset", "ntk_minhash_stats", "ntk_minhash_read", "ntk_minhash_merge",
          "ntk_record_minhash_read", "ntk_record_minhash_stats", "ntk_record_minhash_trim", "ntk_mhset_read", "ntk_mhset_compare",
-         "ntk_kmer_colors_reset", "ntk_kmer_colors_stats")
+         "ntk_kmer_colors_reset", "ntk_kmer_colors_stats",
+         "ntk_minimizer_list_read", "ntk_minimizer_list_stats", "ntk_minimizer_list_trim")
+
+
+def shipped_headers() -> list:
+    """Every .h below include/, as a path relative to it: the walk is recursive, so a header in a directory of its own is seen too."""
+    out = []
+    for folder, _, files in os.walk(INCLUDE):
+        out += [os.path.relpath(os.path.join(folder, f), INCLUDE).replace(os.sep, "/") for f in files if f.endswith(".h")]
+    return sorted(out)
 
 
 def header_text(name: str) -> str:
@@ -149,5 +166,5 @@ def takes_device_pointer(params: str) -> bool:
 def table_markdown() -> str:
     lines = ["| call | class | header | the header's words | GPU test |", "|---|---|---|---|---|"]
     for r in ROWS:
-        lines.append(f"| `{r.function}` | {r.cls} | `{r.header}` ({r.where}) | \"{r.words.replace('/*', '').replace('*/', '').strip()}\" | `{r.test}` |")
+        lines.append(f"| `{r.function}` | {r.cls} | `{r.header}` ({r.where}) | \"{r.words.replace('/*', '').replace('*/', '').strip()}\" | `{r.test if r.file == GPU_TESTS else r.file + '::' + r.test}` |")
     return "\n".join(lines)

@@ -1,4 +1,4 @@
-"""The fixed slices of the structured differential fuzz of the eleven k-mer libraries (tests/_lib_fuzz.py) on a real MI355X: one test per
+"""The fixed slices of the structured differential fuzz of the twelve k-mer libraries (tests/_lib_fuzz.py) on a real MI355X: one test per
 stage and width, each a fixed seed and a fixed number of cases (`_lib_fuzz.SLICES`).  tests/test_lib_fuzz_inputs.py proves without a GPU
 that every slice holds the content kinds, the edge lengths and the two-sided conditions that make it mean something; longer runs go
 through tools/lib_fuzz.py and are recorded under profiles/lib_fuzz/.  Truth is the existing host models; every comparison is exact."""
@@ -65,3 +65,7 @@ def test_dbg_and_its_unitig_batch(sess):
 
 def test_colors_and_the_compacted_batch(sess):
     F.run_slice(sess, "colors")
+
+
+def test_minimizer_list(sess):
+    F.run_slice(sess, "minimizer_list")

@@ -188,6 +188,74 @@ def test_more_tiles_than_one_step_of_the_grid(ctx):
     assert np.all(np.diff(pos)[inside[1:]] > 0)   # positions strictly increase inside a record
 
 
+@pytest.mark.parametrize("k,w,order,path,pre", I.GRID_CASES)
+def test_exact_past_one_step_of_the_grid(ctx, k, w, order, path, pre):
+    """Random 150-base reads over 1.25 steps of the capped grid of ml_select_kernel and ml_scatter_kernel, with the quality stream: every
+    field of every entry against the model - random content, ties, N and masked bases at every tile boundary, blocks of the scatter kernel
+    that walk the record starts along a run of two tiles."""
+    grid = n_cu() * MM.BLOCKS_PER_CU
+    buf, qual, off = I.grid_batch(grid)
+    assert len(buf) > grid * MM.TILE
+    want = MM.csr(MM.entries_of(buf, k, w, path, pre, order, qual, I.CUTOFF), off, len(buf), k)
+    with nt.MinimizerList(k, path, w, order, ctx) as ml:
+        got = listed(ml, upload(buf), len(buf), off, pre, d_qual=upload(qual.tobytes(), fill=0xFF), quality_cutoff=I.CUTOFF)
+        st = ml.stats()
+    assert_csr(got, want, ("exact past one step", k, w, order, path))
+    assert st["n_entries"] == want[1].size > grid and st["n_windows"] == int(want[4].sum()) and st["n_chunks"] == 1
+
+
+def test_record_starts_carried_along_a_blocks_tiles(ctx):
+    """2.25 steps of the capped grid, so a block of ml_scatter_kernel takes three consecutive tiles and carries the record starts it
+    knows from one to the next: 5 000 equal starts inside a tile with entries in front of a tile with entries; a tile without entries
+    that holds 5 000 equal starts, skipped between two tiles with entries of the same block; and two skipped tiles in front of a block's
+    only tile with entries, far into the starts.  Exact, both orders."""
+    k, w = I.CARRY_KW
+    grid = n_cu() * MM.BLOCKS_PER_CU
+    sp, _ = I.carry_batch(grid)
+    assert -(-(sp.n_bytes // MM.TILE) // grid) == 3
+    dev = upload(sp.buf().tobytes())
+    for order in (ML.LEX, ML.HASH):
+        with nt.MinimizerList(k, BITS, w, order, ctx) as ml:
+            got = listed(ml, dev, sp.n_bytes, sp.offsets, NONE)
+            assert ml.stats()["n_chunks"] == 1
+        assert_csr(got, sp.csr(k, w, BITS, NONE, order), ("carried record starts", order))
+        assert got[1].size > 1000 and int(got[1].max()) <= 200 - k
+
+
+# ---- the offsets the header defines, the two other pre-steps ---------------------------------------------------------------------------------
+
+def test_offsets_that_are_not_the_packers(ctx):
+    """The header's sentence on offsets that are not the packer's: offsets[0] > 0, offsets[n_records] < n_bytes, runs of 5 000 equal
+    starts in the middle of a tile with entries and in a stretch of tiles without any, and 36 equal starts in front of the last one (the
+    doubling search of a tile's starts steps over offsets[n_records]).  offsets_out and pos are the header's, entries outside every
+    record's range included.  Six tiles: every block of ml_scatter_kernel has one tile and searches the starts from the first on; the
+    starts a block carries from tile to tile are test_record_starts_carried_along_a_blocks_tiles'."""
+    k, w = I.ODD_KW
+    buf, off = I.odd_offsets_batch()
+    dev = upload(buf)
+    for order in (ML.LEX, ML.HASH):
+        want = MM.csr(MM.entries_of(buf, k, w, BITS, NONE, order), off, len(buf), k)
+        with nt.MinimizerList(k, BITS, w, order, ctx) as ml:
+            got = listed(ml, dev, len(buf), off, NONE)
+            assert ml.stats()["n_records"] == off.size - 1 > 2 * I.ODD_RUN
+        assert_csr(got, want, ("odd offsets", order))
+        assert got[0][0] > 0 and got[0][-1] < got[1].size
+
+
+@pytest.mark.parametrize("path,pre", I.IUPAC_PATH_PRES)
+def test_strip_returns_and_normalize_iupac(ctx, path, pre):
+    """The two pre-steps no other case of this file passes, on records with IUPAC letters of either case, U and u."""
+    k, w = I.IUPAC_KW
+    recs = I.iupac_records()
+    buf, off = pack(recs), MM.packed_offsets(recs)
+    dev = upload(buf)
+    for order in (ML.LEX, ML.HASH):
+        with nt.MinimizerList(k, path, w, order, ctx) as ml:
+            got = listed(ml, dev, len(buf), off, pre)
+        assert_csr(got, MM.lists(recs, k, w, path, pre, order), ("pre-step", path, pre, order))
+        assert got[1].size > 100
+
+
 # ---- 5, 7: the chunk seam and the held list ---------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
@@ -224,6 +292,25 @@ def test_chunk_seam(ctx, chunk_batch, k, w):
             assert aimed.size == 1 and got[4][aimed[0]] == w and int(got[1][aimed[0]]) + k - 1 == e, d
             assert ml.stats()["n_chunks"] == 2
     dev[lo:hi] = ord("N")
+
+
+@pytest.mark.parametrize("k,w", I.CHUNK_KW)
+def test_many_records_around_the_chunk_seam(ctx, chunk_batch, k, w):
+    """Thousands of packed records of 0 .. 300 bases around the seam, in HASH order: the second chunk's blocks of ml_scatter_kernel find
+    their record among all the starts of the first chunk; a record that straddles the seam, a start inside the halo, and starts exactly at
+    the seam and one byte to either side."""
+    dev, _ = chunk_batch
+    with nt.MinimizerList(k, BITS, w, ML.HASH, ctx) as ml:
+        for layout in I.SEAM_LAYOUTS:
+            sr = I.seam_records(k, w, layout)
+            for lo, hi in ((0, 2 * I.EARLY_AT), (I.SEAM_LO - 16, I.SEAM_HI + 16), (I.CHUNK_BYTES - 16, I.CHUNK_BYTES)):
+                _place(dev, sr, lo, hi)
+            n_records = sr.offsets.size - 1
+            ml.run_device(dev, I.CHUNK_BYTES, dev_offsets(sr.offsets), n_records, NONE)
+            assert_csr(ml.read(), sr.csr(k, w, BITS, NONE, ML.HASH), ("many records at the chunk seam", k, w, layout))
+            st = ml.stats()
+            assert st["n_chunks"] == 2 and st["n_records"] == n_records >= 2000
+    dev[I.SEAM_LO - 16: I.SEAM_HI + 16] = ord("N")
 
 
 def test_held_list(ctx, chunk_batch):

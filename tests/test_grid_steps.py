@@ -1,4 +1,4 @@
-"""tests/_grid_steps.py held to the sources: every capped or fixed launch of the eleven k-mer libraries has a row, every row's numbers are
+"""tests/_grid_steps.py held to the sources: every capped or fixed launch of the twelve k-mer libraries has a row, every row's numbers are
 what the source's text evaluates to, and every GPU test a row names exists."""
 import os
 import re
@@ -32,8 +32,8 @@ def statement(text: str, at: int) -> str:
 
 
 def constant(name: str, file: str) -> int:
-    """`constexpr TYPE name = value;` in `file`, or in the scaffold's header."""
-    for f in (file, "ntk_consumer.hpp"):
+    """`constexpr TYPE name = value;` in `file`, in the scaffold's header, or (an ML_ name) in the minimizer list's rule."""
+    for f in (file, "ntk_consumer.hpp") + (("ntk_ml_rule.hpp",) if name.startswith("ML_") else ()):
         m = re.search(rf"^constexpr \w+ {name} = (\d+)u?;", L.no_comments(G.source(f)), re.M)
         if m:
             return int(m.group(1))
@@ -44,7 +44,7 @@ def evaluate(expr: str, file: str) -> int:
     """A C expression of integers, casts and named constants."""
     expr = re.sub(r"\((?:unsigned|uint64_t|uint32_t)\)", "", expr)
     expr = re.sub(r"\b\w+->n_cu\b|\bn_cu\b", "1", expr)
-    expr = re.sub(r"\bk[A-Z]\w*", lambda m: str(constant(m.group(0), file)), expr)
+    expr = re.sub(r"\bk[A-Z]\w*|\bML_[A-Z_]+", lambda m: str(constant(m.group(0), file)), expr)
     expr = re.sub(r"0x[0-9A-Fa-f]+", lambda m: str(int(m.group(0), 16)), expr)
     expr = re.sub(r"(\d)u\b", r"\1", expr).replace("/", "//")
     assert re.fullmatch(r"[\d\s()*/+-]+", expr), expr
@@ -70,6 +70,9 @@ def sites(text: str):
 
 @pytest.mark.parametrize("lib", G.LIBS)
 def test_every_capped_launch_has_its_rows(lib):
+    """`sites` decides what needs a row: a grid_for call, or a dim3 that names n_cu or a local made from it.  Of the minimizer list's four
+    launches that leaves out ml_scan_kernel (dim3(1): one block scans a chunk's tile counts, whatever the device) and ml_offsets_kernel
+    (dim3(blocks_for(n_records + 1)): one thread per record start, no cap and no loop), so neither has a row."""
     rows = [r for r in G.ROWS if r.lib == lib]
     for file in G.files_of(lib):
         text, found = sites(G.source(file))
@@ -93,12 +96,15 @@ def test_every_capped_launch_has_its_rows(lib):
     assert {r.file for r in rows} <= set(G.files_of(lib)), lib
 
 
-def test_the_rows_are_the_eleven_libraries_and_no_launch_is_listed_twice():
-    assert len(G.LIBS) == 11 and {r.lib for r in G.ROWS} == set(G.LIBS)
+def test_the_rows_are_the_twelve_libraries_and_no_launch_is_listed_twice():
+    assert len(G.LIBS) == 12 and {r.lib for r in G.ROWS} == set(G.LIBS)
     keys = [(r.lib, r.kernel) for r in G.ROWS]
     assert len(set(keys)) == len(keys)
     for r in G.ROWS:   # a kernel the inventory names is one the library ships (tests/_libraries.py holds those to the binaries)
-        if r.lib != "colors":
+        if r.lib == "minimizer_list":   # (its row is tests/test_minimizer_list_abi.py's)
+            import test_minimizer_list_abi as ml
+            assert r.kernel in ml.ROW.kernels and G.files_of(r.lib) == (os.path.basename(ml.ROW.hip),) + ml.ROW.headers, r.kernel
+        elif r.lib != "colors":
             assert any(L.bare(k).split("<")[0] == r.kernel for k in L.BY_NAME[r.lib].kernels), r.kernel
 
 
@@ -128,7 +134,7 @@ def test_a_rows_numbers_are_what_its_source_says(row):
 def test_the_kernels_stride_by_what_the_rows_say():
     """The loop of a record kernel steps by its grid's items: the text of the strides the new GPU tests rely on."""
     src = {f: L.no_comments(G.source(f)) for f in ("ntk_abundance.hip", "ntk_colors.hip", "ntk_trim.hip", "ntk_record_minhash.hip",
-                                                   "ntk_kmer_sets.hip", "ntk_dbg.hip")}
+                                                   "ntk_kmer_sets.hip", "ntk_dbg.hip", "ntk_minimizer_list.hip")}
     assert "for (uint64_t i = blockIdx.x; i < n_long; i += gridDim.x)" in src["ntk_abundance.hip"]
     assert "for (uint64_t r = first; r < a.n_records; r += waves)" in src["ntk_colors.hip"]
     assert "screen_rounds(a, lo, hi, first, waves, lane, acc);" in src["ntk_colors.hip"]
@@ -136,6 +142,11 @@ def test_the_kernels_stride_by_what_the_rows_say():
     assert "r < a.b.n_records; r += (uint64_t)gridDim.x * kPerBlock)" in src["ntk_trim.hip"]
     assert "for (uint64_t r = a.r0 + blockIdx.x; r < a.r1; r += gridDim.x)" in src["ntk_record_minhash.hip"]
     assert len(re.findall(r"const uint64_t stride = \(uint64_t\)gridDim\.x \* kThreads", src["ntk_dbg.hip"])) == 10
+    # the minimizer list: the select kernel strides over the tiles, the scatter kernel takes a contiguous run of `per` of them
+    ml = src["ntk_minimizer_list.hip"]
+    assert "for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x)" in ml
+    assert "const uint64_t per = (tiles + gridDim.x - 1) / gridDim.x, t_begin = blockIdx.x * per" in ml
+    assert "for (uint64_t t = t_begin; t < t_end; t++)" in ml
 
 
 def test_the_units_of_the_notes():
@@ -147,6 +158,8 @@ def test_the_units_of_the_notes():
     rmh = L.no_comments(G.source("ntk_record_minhash.hip"))
     assert "constexpr uint64_t kTile = 64 * kPerLane;" in rmh and "constexpr uint64_t kSegment = 4 * kTile * 4;" in rmh
     assert G.K_RMH_SEGMENT == 4 * (64 * 4) * 4
+    file, name, value = G.K_ML_TILE
+    assert constant(name, file) == value
 
 
 def test_every_named_gpu_test_exists():
@@ -167,3 +180,4 @@ def test_items_per_step():
     assert G.items_per_step(G.rows_of("dbg_rows_kernel"), 256) == 1 << 20
     assert G.items_per_step(G.rows_of("rt_interval_kernel"), 304) == 32 * 8 * 304
     assert G.items_per_step(G.rows_of("ks_split_kernel"), 256) is None
+    assert G.items_per_step(G.rows_of("ml_select_kernel"), 256) == G.items_per_step(G.rows_of("ml_scatter_kernel"), 256) == 2048

@@ -12,6 +12,7 @@ import _colors_model as KM
 import _kmer_sets_model as KS
 import _lib_fuzz as F
 import _minhash_model as M
+import _minimizer_list_model as MM
 import _record_minhash_model as RM
 import _trim_model as T
 from _count_helpers import oracle_items, pack
@@ -73,7 +74,8 @@ def test_every_content_kind_and_edge_length_occurs(stage):
         kinds |= set(c.kinds)
         classes |= {x for x in c.classes if x is not None}
         residues |= set((c.starts() % 16).tolist())
-        lengths = F.edge_lengths(c.k, c.stage, c.num())
+        lengths = c.edges()
+        assert lengths == F.edge_lengths(c.k, c.stage, c.num(), c.extra.get("w", 0))
         for r, cls, kind in zip(c.records, c.classes, c.kinds):   # a class is the length it names
             if cls in lengths:
                 assert len(r) == lengths[cls]
@@ -414,3 +416,200 @@ def test_colors_slice_meets_both_sides_of_its_rules():
     assert {KM.LONG_RECORD, KM.LONG_RECORD + 1} <= r["windows"], sorted(w for w in r["windows"] if w > 10000)
     assert r["cut_left"] >= 1 and r["cut_right"] >= 1, r        # the compacted batch that is fed back has records cut on each side
     assert min(r["fed"]) > 0, r                                 # and every case feeds one back
+
+
+# ---- the minimizer_list stage ------------------------------------------------------------------------------------------------------------
+#
+# Everything below is computed from the model alone (`_minimizer_list_model.planes` / `windows` / `csr`) on the packed batch of a case, as
+# the checker's first run takes it: no quality stream, `_trim_model.offsets`.  A tile boundary is a multiple of ML_TILE window ends of
+# that batch (a run starts its tiles at end 0: one chunk).
+
+def test_the_minimizer_list_tile_is_the_rules():
+    rule = open(F.MM.__file__.replace("_minimizer_list_model.py", "../needletail_amd/csrc/ntk_ml_rule.hpp")).read()
+    assert f"constexpr uint32_t ML_TILE = {F.ML_TILE};" in rule and F.ML_TILE == MM.TILE == 1024
+    assert f"constexpr uint32_t ML_W_MAX = {max(max(ws) for ws in F.ML_W_CLASSES.values())};" in rule
+    e = F.edge_lengths(21, "minimizer_list", window=11)
+    assert (e["k+w-2"], e["k+w-1"], e["k+w"], e["k+2w-1"]) == (30, 31, 32, 42)      # no window, one, two, a run of w + 1
+    assert (e["T1023"], e["T1024"], e["T1025"]) == (1043, 1044, 1045)                  # ML_TILE - 1, ML_TILE, ML_TILE + 1 window ends
+    assert set(e) - set(F.edge_lengths(21)) == {"k+w-2", "k+w-1", "k+w", "k+2w-1", "T1023", "T1024", "T1025"}
+    assert F.long_classes("minimizer_list") == () and F.STAGES[-1] == "minimizer_list" and len(F.STAGES) == 12
+    for name, ws in F.ML_W_CLASSES.items():
+        for w in ws:
+            assert (name == "one") == (w == 1) and (name == "power_of_two") == (w > 1 and w & (w - 1) == 0)
+    assert all(any(abs(w - p) == 1 for p in F.ML_W_CLASSES["power_of_two"]) for w in F.ML_W_CLASSES["neighbour"])
+
+
+def ml_windows_rightmost(values, valid, w, order):
+    """`MM.windows` with the other tie rule: of equal smallest keys the RIGHTMOST."""
+    whole, _ = MM.windows(values, valid, w, order)
+    key = MM.keys_of(values, order)
+    e = np.arange(values.size, dtype=np.int64)
+    best, picked = key.copy(), e.copy()
+    for j in range(1, w):             # from the right: only a strictly smaller key replaces the pick
+        at = np.maximum(e - j, 0)
+        take = key[at] < best
+        best[take], picked[take] = key[at][take], at[take]
+    return whole, picked
+
+
+def ml_entries_from(values, strand, whole, picked, force_open=None, span_cap=None, strand_at_first_end=False):
+    """`MM.entries_of` from the planes on: an entry opens where a whole window does not continue the pick of a whole window before it
+    (or where `force_open` says so); its span runs to the next end that does not continue it (`span_cap(e)`: at most that)."""
+    n = values.size
+    before_whole = np.concatenate([[False], whole[:-1]])
+    before_pick = np.concatenate([[-1], picked[:-1]])
+    opens = whole & ~(before_whole & (before_pick == picked))
+    if force_open is not None:
+        opens |= whole & force_open
+    e = np.flatnonzero(opens)
+    stop = np.append(np.flatnonzero(~(whole & ~opens)), n)
+    span = stop[np.searchsorted(stop, e, side="right")] - e
+    if span_cap is not None:
+        span = np.minimum(span, span_cap(e))
+    a = picked[e]
+    return MM.Entries(e, a, values[a], strand[e] if strand_at_first_end else strand[a], span)
+
+
+def ml_wrong_rules(c, values, valid, strand):
+    """name -> the entries a kernel with that defect would hold (the planted wrong rules)."""
+    k, w, order = c.k, c.extra["w"], c.extra["order"]
+    T = F.ML_TILE
+    whole, picked = MM.windows(values, valid, w, order)
+    e = np.arange(values.size, dtype=np.int64)
+    out = {}
+    out["rightmost on ties"] = ml_entries_from(values, strand, *ml_windows_rightmost(values, valid, w, order))
+    # every tile its own batch: a window whose first end lies in the tile before is not whole (nothing in front of a tile is read)
+    out["no halo"] = ml_entries_from(values, strand, whole & (e - (w - 1) >= e // T * T), picked)
+    out["an entry opens at every tile start"] = ml_entries_from(values, strand, whole, picked, force_open=e % T == 0)
+    out["span cut at the tile end"] = ml_entries_from(values, strand, whole, picked, span_cap=lambda x: (x // T + 1) * T - x)
+    out["the order swapped"] = ml_entries_from(values, strand, *MM.windows(values, valid, w, MM.HASH if order == MM.LEX else MM.LEX))
+    out["the strand of the first window end"] = ml_entries_from(values, strand, whole, picked, strand_at_first_end=True)
+    return out
+
+
+ML_WRONG = ("rightmost on ties", "no halo", "an entry opens at every tile start", "span cut at the tile end", "the order swapped",
+            "the strand of the first window end")
+
+
+def _same_csr(a, b):
+    return all(np.asarray(x).shape == np.asarray(y).shape and np.array_equal(np.asarray(x).astype(np.uint64), np.asarray(y).astype(np.uint64))
+               for x, y in zip(a, b))
+
+
+def ml_case_report(rng, c) -> dict:
+    """What one case of the stage contributes to the slice's conditions."""
+    k, w, order, T = c.k, c.extra["w"], c.extra["order"], F.ML_TILE
+    buf, off = c.buf(), c.offsets()
+    values, valid, strand = MM.planes(buf, k, c.path, c.pre)
+    whole, picked = MM.windows(values, valid, w, order)
+    ent = MM.entries_of(buf, k, w, c.path, c.pre, order)
+    true = MM.csr(ent, off, len(buf), k)
+    assert _same_csr(true, MM.csr(ml_entries_from(values, strand, whole, picked), off, len(buf), k))   # the variants' frame is the model's
+    assert _same_csr(true, F.ml_want(c, False))
+    last = ent.end + ent.span.astype(np.int64) - 1
+    # boundaries B = j * T with an entry whose windows [e, e + span) end on both sides of it: e < B <= e + span - 1
+    straddled = {int(b) for b in (last // T * T)[(ent.end // T) < (last // T)]}
+    # a window with two or more equal smallest keys whose leftmost lies in the tile before the window's end
+    _, right = ml_windows_rightmost(values, valid, w, order)
+    x = np.flatnonzero(whole & (right != picked))
+    ties_across = int((picked[x] // T < x // T).sum())
+    # records without a window; records whose run of whole windows is cut, told apart by the byte that cuts it: a junk byte of
+    # `junk_bytes(pre)` that is no N (without the quality stream), or a base that the quality stream masks (with it)
+    starts, ends = off[:-1].astype(np.int64), off[1:].astype(np.int64)
+    n_whole = np.searchsorted(np.flatnonzero(whole), ends) - np.searchsorted(np.flatnonzero(whole), starts)
+    a = np.frombuffer(buf, dtype=np.uint8)
+    junk = np.setdiff1d(F.junk_bytes(c.pre), np.frombuffer(b"Nn", dtype=np.uint8))
+    cut_junk = len({int(r) for r, p in ml_cuts(whole, off) if a[p] in junk})
+    qs = c.qual_stream()
+    whole_q, _ = MM.windows(*MM.planes(buf, k, c.path, c.pre, qs, c.cutoff)[:2], w, order)
+    bases = np.frombuffer(b"ACGTacgt" + (b"Uu" if c.pre >= MM.PRE_NORMALIZE else b""), dtype=np.uint8)
+    cut_masked = len({int(r) for r, p in ml_cuts(whole_q, off) if c.cutoff and a[p] in bases and qs[p] < c.cutoff})
+    # the picked k-mer's start and the first window end lie in the same record: a whole window holds no break byte
+    rec_of = lambda p: np.searchsorted(starts, p, side="right")   # noqa: E731
+    same_record = bool(np.array_equal(rec_of(ent.picked - (k - 1)), rec_of(ent.end)))
+    wrong = {name: not _same_csr(true, MM.csr(bad, off, len(buf), k)) for name, bad in ml_wrong_rules(c, values, valid, strand).items()}
+    d = F.draw_ml(_copy(rng), c)
+    second = F.ml_second_case(_copy_after(rng, c), c, d)
+    return dict(order=order, path_pre=(c.path, c.pre), w=w, masked=not _same_csr(true, F.ml_want(c, True)), straddled=len(straddled),
+                ties_across=ties_across, span1=int((ent.span == 1).sum()), span_w=int(((ent.span == w) & (w > 1)).sum()),
+                span_mid=int(((ent.span > 1) & (ent.span < w)).sum()), no_window=int((n_whole == 0).sum()), cut_junk=cut_junk, cut_masked=cut_masked, same_record=same_record,
+                wrong=wrong, prefix=d["prefix"], n_records=len(c.records), second_smaller=len(second.buf()) < len(buf),
+                second_entries=len(F.ml_entries(second, d["second_q"])[0]), entries=len(ent))
+
+
+def ml_cuts(whole, off):
+    """(record, p) where a record's run of whole windows is cut: the window that ends at p - 1 is whole, the one that ends at p is not -
+    so byte p is no base - and a later window of the same record is whole again."""
+    ends = np.flatnonzero(whole)
+    rec = np.searchsorted(off.astype(np.int64), ends, side="right") - 1
+    gap = np.flatnonzero((np.diff(ends) > 1) & (rec[1:] == rec[:-1]))
+    return [(rec[i], ends[i] + 1) for i in gap]
+
+
+def _copy_after(rng, c):
+    """A generator in the state the checker's is in after `draw_ml`."""
+    g = _copy(rng)
+    F.draw_ml(g, c)
+    return g
+
+
+def ml_slice_report(reports) -> dict:
+    reports = list(reports)
+    pow2 = lambda w: w & (w - 1) == 0   # noqa: E731
+    cls = lambda w: next(name for name, ws in F.ML_W_CLASSES.items() if w in ws)   # noqa: E731
+    return dict(orders={r["order"] for r in reports}, path_pres={r["path_pre"] for r in reports}, w_classes={cls(r["w"]) for r in reports},
+                masked=sum(r["masked"] for r in reports), straddled=sum(r["straddled"] for r in reports),
+                straddled_hash=sum(r["straddled"] for r in reports if r["order"] == MM.HASH),
+                straddled_not_pow2=sum(r["straddled"] for r in reports if not pow2(r["w"])),
+                ties_across=sum(r["ties_across"] for r in reports), span1=sum(r["span1"] for r in reports),
+                span_w=sum(r["span_w"] for r in reports), span_mid=sum(r["span_mid"] for r in reports),
+                no_window=sum(r["no_window"] for r in reports), cut_junk=sum(r["cut_junk"] for r in reports),
+                cut_masked=sum(r["cut_masked"] for r in reports),
+                same_record=all(r["same_record"] for r in reports),
+                wrong={name: sum(r["wrong"][name] for r in reports) for name in ML_WRONG},
+                second=all(r["second_smaller"] for r in reports) and sum(r["second_entries"] > 0 for r in reports),
+                prefix=sum(r["prefix"] < r["n_records"] for r in reports))
+
+
+def ml_conditions(r) -> list:
+    """The conditions of the slice that do not hold (none: the slice means something)."""
+    miss = []
+    if r["orders"] != set(F.ML_ORDERS):
+        miss.append("both orders")
+    if r["path_pres"] != set(F.PATH_PRES):
+        miss.append("every (path, pre) pair")
+    if r["w_classes"] != set(F.ML_W_CLASSES):
+        miss.append("all four classes of w")
+    if r["masked"] < 1:
+        miss.append("a quality mask that changes the CSR")
+    if r["straddled"] < 8 or r["straddled_hash"] < 2 or r["straddled_not_pow2"] < 2:
+        miss.append("8 straddled tile boundaries, 2 under HASH, 2 with w not a power of two")
+    if r["ties_across"] < 1:
+        miss.append("a tie whose leftmost pick lies across a tile boundary")
+    if min(r["span1"], r["span_w"], r["span_mid"]) < 1:
+        miss.append("spans 1, w and between")
+    if r["no_window"] < 1 or r["cut_junk"] < 1 or r["cut_masked"] < 1:
+        miss.append("a record without a window, one whose run of windows is cut by a junk byte and one where a masked base cuts it")
+    miss += [f"wrong rule: {name}" for name, n in r["wrong"].items() if n < 1]
+    if not r["second"] or r["prefix"] < 1:
+        miss.append("a smaller second case with entries, a proper prefix")
+    return miss
+
+
+def test_minimizer_list_slice_meets_the_tile_boundaries_and_sees_every_planted_wrong_rule():
+    reports = [ml_case_report(rng, c) for rng, c in cases("minimizer_list")]
+    r = ml_slice_report(reports)
+    assert ml_conditions(r) == [], r
+    # `pos` relative to the record of the picked k-mer's start instead of the record of the first window end is no variant: with the
+    # packer's offsets the two never differ.  A whole window is w + k - 1 good bases that end at the first window end, the picked k-mer
+    # lies inside them, and every record ends with a break byte, which is no base: no record start lies between the two.
+    assert r["same_record"]
+    assert set(r["wrong"]) == set(ML_WRONG)
+
+
+PINNED_NEWER = {"minimizer_list": ("915c437abf63380e3c45f19a0ee185a03e723827a6d22404ef024e7ebec1e5fd", (101, 15))}
+
+
+def test_the_minimizer_list_slice_is_pinned():
+    digest, size = PINNED_NEWER["minimizer_list"]
+    assert F.SLICES["minimizer_list"] == size and F.slice_digest("minimizer_list") == digest

@@ -167,3 +167,118 @@ def test_device_bytes_restates_the_header():
     bases = MM.CHUNK + 288 + 255 + 1      # the halo of k + w = 288, the tail w - 1, up to a multiple of 16
     assert MM.halo(32, 256) == 288 and bases % 16 == 0
     assert two == bases * 8 + bases // 16 * 4 + bases * 2 + 2 * (65537 + 1) * 4 + 16 + MM.grow_half_again(2) * 8 + MM.grow_half_again(304) * 28
+
+
+# ---- the inputs of the exact cases: the capped grid, many records at the chunk seam, odd offsets, the two other pre-steps ------------------
+
+@pytest.mark.parametrize("k,w,order,path,pre", I.GRID_CASES)
+def test_grid_batch_is_random_masked_and_crosses_tiles(k, w, order, path, pre):
+    """At a grid of 64 blocks (the GPU test sizes it from the device): more than one step of tiles, entries of both strands across tile
+    boundaries, and a quality stream that changes the result."""
+    grid = 64
+    buf, qual, off = I.grid_batch(grid)
+    assert grid * MM.TILE < len(buf) < 1.3 * grid * MM.TILE and off[-1] == len(buf) and qual.size == len(buf) and set(np.diff(off).tolist()) == {151}
+    ent = MM.entries_of(buf, k, w, path, pre, order, qual, I.CUTOFF)
+    plain = MM.entries_of(buf, k, w, path, pre, order)
+    assert len(ent) != len(plain) and int(ent.span.sum()) < int(plain.span.sum())
+    last = ent.end + ent.span.astype(np.int64) - 1
+    assert int((ent.end // MM.TILE < last // MM.TILE).sum()) > grid // 4, "entries whose windows end on both sides of a tile boundary"
+    assert (ent.strand == 0).any() and (ent.strand == 1).any() and (ent.end >= grid * MM.TILE).any()
+    assert I.GRID_STEPS == 1.25 and {c[2] for c in I.GRID_CASES} == {MM.LEX, MM.HASH}
+
+
+@pytest.mark.parametrize("k,w", I.CHUNK_KW)
+def test_seam_records_put_many_records_on_both_sides(k, w):
+    starts_seen, halo_start, straddler = set(), False, False
+    for layout in I.SEAM_LAYOUTS:
+        sr = I.seam_records(k, w, layout)
+        s = sr.offsets.astype(np.int64)
+        assert len(s) - 1 >= 2000 and s[0] == 0 and s[1] == I.SEAM_LO and s[-1] == I.CHUNK_BYTES and s[-2] <= I.SEAM_HI and np.all(np.diff(s) >= 1)
+        assert max(len(r) for r in sr.records) == I.SEAM_LONG and min(len(r) for r in sr.records) == 0
+        region = sr.region(I.SEAM_LO - 16, I.SEAM_HI + 16)
+        assert np.all(region[s[1:-1] - 1 - (I.SEAM_LO - 16)] == ord("\n")) and region.tobytes()[16:16 + s[-2] - I.SEAM_LO] == b"".join(r + b"\n" for r in sr.records)
+        ent = sr.entries(k, w, MM.PATH_BITS, MM.PRE_NONE, MM.HASH)
+        rec = np.searchsorted(s, ent.end, side="right") - 1
+        first, second = ent.end < MM.CHUNK, ent.end >= MM.CHUNK
+        assert (ent.end[first] < 2 * I.EARLY_AT).any(), "the early piece"
+        assert len(set(rec[first & (ent.end >= I.SEAM_LO)])) >= 3 and len(set(rec[second])) >= 3, "entries in three records or more on each side"
+        straddler |= bool(((s[rec] < MM.CHUNK) & second).any())   # the record starts in the first chunk, the entry's first window ends in the second
+        starts_seen |= {int(x) - MM.CHUNK for x in s if abs(int(x) - MM.CHUNK) <= 1}
+        halo_start |= bool(((s >= MM.CHUNK - MM.halo(k, w)) & (s < MM.CHUNK)).any())
+        assert ((s[:-1] < MM.CHUNK) & (s[1:] > MM.CHUNK)).sum() == (layout == "straddle")   # a record with bytes on both sides of the seam
+        want = MM.csr(ent, sr.offsets, sr.n_bytes, k)
+        assert want[0][0] == 0 and want[0][-1] == len(ent) and int(want[1][int(want[0][1]):].max()) <= I.SEAM_LONG - k
+    assert starts_seen == {-1, 0, 1} and halo_start and straddler
+
+
+def test_odd_offsets_are_what_the_header_defines_and_the_packer_never_makes():
+    k, w = I.ODD_KW
+    buf, off = I.odd_offsets_batch()
+    T = MM.TILE
+    assert len(buf) == I.ODD_TILES * T >= 5 * T and np.all(np.diff(off.astype(np.int64)) >= 0) and off[0] > 0 and off[-1] < len(buf)
+    values, counts = np.unique(off, return_counts=True)
+    runs = values[counts == I.ODD_RUN].astype(np.int64)
+    assert runs.size == 2 and sorted(counts.tolist())[:-3] == [1] * (values.size - 3)
+    # starts_from searches from the first of the ODD_TAIL equal starts (the start before them is the tile's first end) at from + 0, 1, 3,
+    # 7, ...: it steps over offsets[n_records], whose own value only the search between the last two steps finds
+    assert counts[-1] == 1 and counts[-2] == I.ODD_TAIL and values[-3] == 5 * T and I.ODD_TAIL not in [2 ** i - 1 for i in range(8)]
+    for order in (MM.LEX, MM.HASH):
+        ent = MM.entries_of(buf, k, w, MM.PATH_BITS, MM.PRE_NONE, order)
+        per_tile = np.bincount(ent.end // T, minlength=I.ODD_TILES)
+        assert per_tile[runs[0] // T] > 0 and runs[0] % T in range(T // 4, 3 * T // 4), "a run in the middle of a tile with entries"
+        assert per_tile[runs[1] // T] == 0 and per_tile[runs[1] // T + 1] == 0 and per_tile[runs[1] // T + 2] > 0, "a run in tiles without entries"
+        assert (ent.end[ent.end > runs[0]] // T == runs[0] // T).any() and (ent.end[ent.end < runs[0]] // T == runs[0] // T).any()
+        out, pos, _, _, _ = MM.csr(ent, off, len(buf), k)
+        assert out[0] > 0 and out[-1] < len(ent), "entries in front of offsets[0] and behind offsets[n_records]: outside every range"
+        assert np.all(np.diff(out.astype(np.int64)) >= 0) and int(pos.max()) < 2 * T   # no start inside a window: no pos wraps
+        assert (ent.end >= int(values[-1])).any() and ((ent.end >= int(values[-2])) & (ent.end < int(values[-1]))).any()
+
+
+def test_iupac_records_hold_what_the_two_pre_steps_differ_on():
+    k, w = I.IUPAC_KW
+    recs = I.iupac_records()
+    text = b"".join(recs)
+    assert set(b"RYKMSWBDHVN") & set(text) and set(b"rykmswbdhvn") & set(text) and b"U" in text and b"u" in text and not set(b"\r\n \t") & set(text)
+    assert {p for _, p in I.IUPAC_PATH_PRES} == {MM.PRE_STRIP_RETURNS, MM.PRE_NORMALIZE_IUPAC}
+    assert {p for p, pre in I.IUPAC_PATH_PRES if pre == MM.PRE_NORMALIZE_IUPAC} == {MM.PATH_BYTES_CANONICAL, MM.PATH_BITS, MM.PATH_BITS_CANONICAL}
+    strip = MM.lists(recs, k, w, MM.PATH_BITS, MM.PRE_STRIP_RETURNS, MM.HASH)
+    iupac = MM.lists(recs, k, w, MM.PATH_BITS, MM.PRE_NORMALIZE_IUPAC, MM.HASH)
+    assert strip[1].size > 100 and iupac[1].size > 100 and int(iupac[4].sum()) > int(strip[4].sum()), "U is a base for NORMALIZE_IUPAC only"
+
+
+@pytest.mark.parametrize("cu", [256, 304])
+def test_carry_batch_puts_skipped_tiles_and_runs_of_starts_inside_one_blocks_tiles(cu):
+    """ml_scatter_kernel: `per = ceil(tiles / gridDim.x)` consecutive tiles a block, the starts known at the end of one tile carried to
+    the next, a tile without entries skipped.  At a capped grid of cu * ML_BLOCKS_PER_CU blocks the batch has per = 3, and the tiles of
+    each of its three blocks are the same block's."""
+    k, w = I.CARRY_KW
+    grid, T = cu * MM.BLOCKS_PER_CU, MM.TILE
+    sp, blocks = I.carry_batch(grid)
+    n_tiles = sp.n_bytes // T
+    assert sp.n_bytes % T == 0 and n_tiles > 2 * grid and min(n_tiles, grid) == grid
+    per = -(-n_tiles // grid)   # `per` of the kernel at gridDim.x = grid_for(own_tiles, 1, resident) = grid
+    assert per == 3
+    scatter = open(I.MM.__file__.replace("_minimizer_list_model.py", "../needletail_amd/csrc/ntk_minimizer_list.hip")).read()
+    assert "const uint64_t per = (tiles + gridDim.x - 1) / gridDim.x, t_begin = blockIdx.x * per" in scatter
+    assert "if (a.tile_base[t + 1] == a.tile_base[t]) continue;" in scatter and "uint64_t j_hi = 0;" in scatter
+    s = sp.offsets.astype(np.int64)
+    assert np.all(np.diff(s) >= 0) and s[-1] == sp.n_bytes and s.size - 1 > 2 * I.CARRY_RUN
+    for order in (MM.LEX, MM.HASH):
+        ent = sp.entries(k, w, MM.PATH_BITS, MM.PRE_NONE, order)
+        per_tile = np.bincount(ent.end // T, minlength=n_tiles)
+        in_tile = lambda t: int(((s >= t * T) & (s < (t + 1) * T)).sum())   # noqa: E731
+        for name, t in blocks.items():
+            assert t % per == 0 and {x // per for x in (t, t + 1, t + 2)} == {t // per}, (name, "one block's three tiles")
+        t = blocks["early"]   # the run lies in a tile with entries, at a record start, and the block's next tile has entries
+        assert per_tile[t] > 0 and per_tile[t + 1] > 0 and per_tile[t + 2] == 0 and in_tile(t) > I.CARRY_RUN
+        run = np.flatnonzero(np.bincount(s[(s >= t * T) & (s < (t + 1) * T)] - t * T) >= I.CARRY_RUN)
+        assert run.size == 1 and T // 4 < run[0] < 3 * T // 4 and sp.buf()[t * T + run[0] - 1] == ord("\n")
+        assert ((ent.end // T == t) & (ent.end > t * T + run[0])).any() and ((ent.end // T == t) & (ent.end < t * T + run[0])).any()
+        t = blocks["mid"]     # entries, none (the run of equal starts is there), entries: the skipped tile and the next one are one block's
+        assert per_tile[t] > 0 and per_tile[t + 1] == 0 and per_tile[t + 2] > 0 and in_tile(t + 1) == I.CARRY_RUN
+        assert int((s < t * T).sum()) > I.CARRY_RUN, "many starts behind the block"
+        t = blocks["late"]    # none, none, entries: nothing is known when the third tile is reached
+        assert per_tile[t] == 0 and per_tile[t + 1] == 0 and per_tile[t + 2] > 0 and in_tile(t + 1) == 100
+        assert int((s <= (t + 2) * T).sum()) > 2 * I.CARRY_RUN
+        want = MM.csr(ent, sp.offsets, sp.n_bytes, k)
+        assert want[0][-1] == len(ent) and int(want[1].max()) <= 200 - k, "every pos is inside its record of at most 200 bases"

@@ -16,7 +16,7 @@ CSRC = os.path.join(SC.ROOT, "needletail_amd", "csrc")
 
 
 def declared():
-    """function -> (header, parameter text, comment text next to it) over the twelve headers."""
+    """function -> (header, parameter text, comment text next to it) over the thirteen headers."""
     out = {}
     for header in SC.HEADERS:
         for name, params, near in SC.declarations(SC.header_text(header)):
@@ -25,9 +25,11 @@ def declared():
     return out
 
 
-def test_the_twelve_headers_are_the_ones_that_ship():
-    shipped = sorted(f for f in os.listdir(SC.INCLUDE) if re.fullmatch(r"needletail_amd(_\w+)?\.h", f))
-    assert shipped == sorted(SC.HEADERS) and len(SC.HEADERS) == 12
+def test_the_thirteen_headers_are_the_ones_that_ship():
+    """Every header below include/, whatever its directory: the twelve needletail_amd(_NAME).h and those of include/needletail_amd/."""
+    shipped = SC.shipped_headers()
+    assert all(re.fullmatch(r"needletail_amd(_\w+)?\.h|needletail_amd/\w+\.h", f) for f in shipped), shipped
+    assert shipped == sorted(SC.HEADERS) and len(SC.HEADERS) == 13
 
 
 def test_every_device_face_declaration_has_a_row():
@@ -62,6 +64,8 @@ def test_a_rows_words_are_the_headers(row):
         assert SC.plain(row.words) in head, (row.function, "the words are not in the head comment")
         # the head comment's sentence covers the call: it speaks of every call, or names this one's verb
         verb = row.function.replace("_device", "").rsplit("_", 1)[1]
+        if row.header == SC.HEADERS[-1] and row.function.endswith("_device"):   # the minimizer list's sentence says "run_device"
+            verb += "_device"
         assert "Every call" in row.words or re.search(rf"\b{verb}\b", row.words), (row.function, verb)
     # the class is what the words say
     said = SC.plain(row.words).lower()
@@ -74,25 +78,32 @@ def test_a_rows_words_are_the_headers(row):
 
 
 def test_every_row_names_a_gpu_test_that_exists():
-    text = open(os.path.join(TESTS, SC.GPU_TESTS)).read()
-    assert re.search(r"^pytestmark = pytest\.mark\.gpu", text, re.M)
+    texts = {f: open(os.path.join(TESTS, f)).read() for f in {r.file for r in SC.ROWS}}
+    assert SC.GPU_TESTS in texts and set(texts) == {SC.GPU_TESTS, "test_gpu_minimizer_list.py"}
+    assert all(r.file == SC.GPU_TESTS or r.function.startswith("ntk_minimizer_list_") for r in SC.ROWS)   # a row's own file is its library's
+    for text in texts.values():
+        assert re.search(r"^pytestmark = pytest\.mark\.gpu", text, re.M)
     for row in SC.ROWS:
+        text = texts[row.file]
         m = re.search(rf"^def {re.escape(row.test)}\(.*?(?=^def |^class |\Z)", text, re.M | re.S)
         assert m, (row.function, row.test)
     # and the call is made in that file: by name through ctypes, or through the handle's entry or facade method of that name
     for row in SC.ROWS:
-        short = re.sub(r"^ntk_(kmer_table|wide_table|kmer_sketch|minhash|read_abundance|read_trim|record_minhash|mhset|kmer_sets|dbg|kmer_colors)_", "", row.function)
+        text = texts[row.file]
+        short = re.sub(r"^ntk_(kmer_table|wide_table|kmer_sketch|minhash|read_abundance|read_trim|record_minhash|mhset|kmer_sets|dbg|kmer_colors|minimizer_list)_", "", row.function)
         facade = {"ntk_reduce_device_quality": "reduce_device", "ntk_kmer_table_extract_device": "extract(", "ntk_wide_table_extract_device": "extract(",
                   "ntk_minhash_read": ".hashes()", "ntk_record_minhash_read": ".sketches", "ntk_mhset_read": ".sketch(", "ntk_batch_submit": ".submit(",
                   "ntk_kmer_table_stats": ".stats()", "ntk_wide_table_stats": ".stats()", "ntk_kmer_sketch_registers": ".registers()",
-                  "ntk_kmer_sketch_estimate": ".estimate()", "ntk_record_minhash_stats": ".stats()", "ntk_record_minhash_trim": "rmh.trim"}.get(row.function)
+                  "ntk_kmer_sketch_estimate": ".estimate()", "ntk_record_minhash_stats": ".stats()", "ntk_record_minhash_trim": "rmh.trim",
+                  "ntk_minimizer_list_result_device": ".device_arrays()", "ntk_minimizer_list_stats": ".stats()"}.get(row.function)
         names = [row.function, row.function.replace("ntk_", "", 1) + "(", f'"{short}"', f".{short}(", facade]
         assert any(n and n in text for n in names), (row.function, names)
 
 
 def test_the_inventory_table_of_the_profile_is_this_one():
     readme = os.path.join(SC.ROOT, "profiles", "stream_order", "README.md")
-    assert SC.table_markdown() in open(readme).read(), "profiles/stream_order/README.md: regenerate the table from _stream_contract.table_markdown()"
+    text = open(readme).read()   # the whole table: a blank line follows its last row, so rows taken off the end are missed too
+    assert SC.table_markdown() + "\n\n" in text, "profiles/stream_order/README.md: regenerate the table from _stream_contract.table_markdown()"
 
 
 def test_what_the_growth_cases_rely_on_in_the_sources():

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Time-budgeted structured differential fuzz of the eleven k-mer libraries (count table, wide count table, HyperLogLog sketch, read
+"""Time-budgeted structured differential fuzz of the twelve k-mer libraries (count table, wide count table, HyperLogLog sketch, read
 abundance, read trimmer and its batch writer, MinHash, per-record MinHash with the sketch set, k-mer set algebra narrow and wide, the
-de Bruijn graph, the coloured index) against the host models of tests/ - the generator and the checkers are tests/_lib_fuzz.py, whose
+de Bruijn graph, the coloured index, the minimizer lists) against the host models of tests/ - the generator and the checkers are tests/_lib_fuzz.py, whose
 fixed slices run in the suite (tests/test_gpu_lib_fuzz.py).  Needs a gfx950 device, but for --dump.  --stage takes any of
-`_lib_fuzz.STAGES`: count, count_wide, minhash, minhash_wide, abundance, trim, record_minhash, kmer_sets, kmer_sets_wide, dbg, colors.
+`_lib_fuzz.STAGES`: count, count_wide, minhash, minhash_wide, abundance, trim, record_minhash, kmer_sets, kmer_sets_wide, dbg, colors,
+minimizer_list.
 
     python tools/lib_fuzz.py --seconds 180 --seed 1 > profiles/lib_fuzz/<name>.log
     python tools/lib_fuzz.py --seed 1 --stage trim --replay-it 17            # the device work of that case alone

@@ -21,6 +21,7 @@ from .minimizer_lists import HASH, LEX, MinimizerList
 from .seeding import SeedIndex
 from .chaining import AnchorChains
 from .mapping import ChainMappings, ReadMapper
+from .aligning import ChainAlignments, cigar_string
 from .parser import (FastxReader, NeedletailError, Record, decode_phred, parse_fastx_file, parse_fastx_stdin, parse_fastx_string, scan_file,
                      write_fasta, write_fastq,
                      scan_file_parallel)
@@ -31,7 +32,7 @@ from .sequence import (bit_kmers, bit_kmers_arrays, bit_kmers_batch, canonical_k
                        bitmer_to_bytes, bytes_to_bitmer)
 
 __all__ = [
-    "Context", "Batch", "default_context", "NtkError", "KmerTable", "WideKmerTable", "KmerSketch", "ReadAbundance", "ReadTrimmer", "KmerMinHash", "MinHashSet", "RecordMinHash", "KmerSet", "KmerGraph", "KmerColors", "MinimizerList", "LEX", "HASH", "SeedIndex", "AnchorChains", "ChainMappings", "ReadMapper",
+    "Context", "Batch", "default_context", "NtkError", "KmerTable", "WideKmerTable", "KmerSketch", "ReadAbundance", "ReadTrimmer", "KmerMinHash", "MinHashSet", "RecordMinHash", "KmerSet", "KmerGraph", "KmerColors", "MinimizerList", "LEX", "HASH", "SeedIndex", "AnchorChains", "ChainMappings", "ReadMapper", "ChainAlignments", "cigar_string",
     "PATH_BYTES_CANONICAL", "PATH_BITS", "PATH_BITS_CANONICAL",
     "PRE_NONE", "PRE_STRIP_RETURNS", "PRE_NORMALIZE", "PRE_NORMALIZE_IUPAC",
     "parse_fastx_file", "parse_fastx_stdin", "decode_phred", "write_fasta", "write_fastq", "parse_fastx_string", "FastxReader", "Record", "NeedletailError", "scan_file", "scan_file_parallel",

@@ -180,10 +180,13 @@ class ReadMapper:
         self.refs = MinimizerList(k, L.PATH_BITS_CANONICAL, w, order, self.ctx)
         self.reads = MinimizerList(k, L.PATH_BITS_CANONICAL, w, order, self.ctx)
         self.seeds, self.chains, self.mappings = SeedIndex(self.ctx), AnchorChains(self.ctx), ChainMappings(self.ctx)
+        self.alignments = None    # a ChainAlignments, made by the first map_aligned
+        self._ref_batch = None    # the reference batch index() was given
 
     def close(self):
-        for h in (self.mappings, self.chains, self.seeds, self.reads, self.refs):
-            h.close()
+        for h in (self.alignments, self.mappings, self.chains, self.seeds, self.reads, self.refs):
+            if h is not None:
+                h.close()
 
     def __enter__(self):
         return self
@@ -192,14 +195,17 @@ class ReadMapper:
         self.close()
 
     def index(self, dev, n_bytes: int, offsets, n_records: int, pre: int = L.PRE_NORMALIZE):
-        """List and index the references: a device batch and its n_records + 1 record offsets on the device."""
+        """List and index the references: a device batch and its n_records + 1 record offsets on the device.  The batch is remembered
+        for map_aligned, which reads its bases: the caller keeps `dev` and `offsets` alive and unchanged until the last map_aligned."""
         self.refs.run_device(dev, n_bytes, offsets, n_records, pre)
         self.seeds.build(self.refs)
+        self._ref_batch = (dev, n_bytes, offsets, n_records)
 
     def index_records(self, records, pre: int = L.PRE_NORMALIZE):
         """index() of host sequences, packed and uploaded by the batch packer."""
         self.refs.run_records(records, pre)
         self.seeds.build(self.refs)
+        self._ref_batch = None    # (the packer's upload is not kept: map_aligned needs index())
 
     def map(self, dev, n_bytes: int, offsets, n_reads: int, pre: int = L.PRE_NORMALIZE, max_occ: int = 0, max_dist: int = 5000, bw: int = 500,
             h: int = 64, min_score: int = 40, min_cnt: int = 3, mask_level: float = 0.5, pri_ratio: float = 0.8, best_n: int = 5):
@@ -207,6 +213,22 @@ class ReadMapper:
         secondaries, read by read and by rank within a read.  Only those rows leave the device."""
         self.reads.run_device(dev, n_bytes, offsets, n_reads, pre)
         return self._map(max_occ, max_dist, bw, h, min_score, min_cnt, mask_level, pri_ratio, best_n)
+
+    def map_aligned(self, dev, n_bytes: int, offsets, n_reads: int, pre: int = L.PRE_NORMALIZE, max_occ: int = 0, max_dist: int = 5000,
+                    bw: int = 500, h: int = 64, min_score: int = 40, min_cnt: int = 3, mask_level: float = 0.5, pri_ratio: float = 0.8,
+                    best_n: int = 5, a: int = 2, b: int = 4, q: int = 4, e: int = 2, band_pad: int = 64, max_seg: int = 2048, work_mib: int = 0):
+        """map(), then every reported chain aligned base by base (ChainAlignments): (mappings, rows, scores, g_offsets, cigar), the
+        structured array of map() and, entry by entry in the order of its rows, what ChainAlignments.read returns.  The references must
+        have been indexed by index(), whose batch is read here; after index_records this raises ValueError."""
+        if self._ref_batch is None:
+            raise ValueError("map_aligned reads the reference batch: index the references with index(), not index_records()")
+        from .aligning import ChainAlignments
+        got = self.map(dev, n_bytes, offsets, n_reads, pre, max_occ, max_dist, bw, h, min_score, min_cnt, mask_level, pri_ratio, best_n)
+        if self.alignments is None:
+            self.alignments = ChainAlignments(self.ctx)
+        self.alignments.run(self._ref_batch, (dev, n_bytes, offsets, n_reads), self.chains, self.seeds, self.mappings, self.k, a, b, q, e, band_pad,
+                            max_seg, work_mib)
+        return (got,) + self.alignments.read()
 
     def map_records(self, records, pre: int = L.PRE_NORMALIZE, **kw):
         """map() of host sequences, packed and uploaded by the batch packer."""

@@ -1,6 +1,7 @@
-"""A seeded, structured, differential fuzz of the twelve k-mer libraries (count table, wide count table, HyperLogLog sketch, read
+"""A seeded, structured, differential fuzz of sixteen libraries in thirteen stages: the twelve k-mer libraries (count table, wide count table, HyperLogLog sketch, read
 abundance, read trimmer with its batch writer, MinHash; per-record MinHash, the sketch set, k-mer set algebra narrow and wide, the de
-Bruijn graph, the coloured index; the minimizer lists) against the host models the suite already has.  Shared by tests/test_lib_fuzz_inputs.py (CPU: the
+Bruijn graph, the coloured index; the minimizer lists) and the read-mapping pipeline (seed index, chains, mappings, alignments: the
+stage `map_reads`) against the host models the suite already has.  Shared by tests/test_lib_fuzz_inputs.py (CPU: the
 slices are not vacuous), tests/test_gpu_lib_fuzz.py (the fixed slices) and tools/lib_fuzz.py (time-budgeted runs, replay, dump).
 Importable without a GPU: torch is imported only inside the device functions.
 
@@ -34,6 +35,15 @@ the statistics, the result where it lies on the device, the digest to the core's
 second, smaller batch on the same handle.  A case's batch is 6 .. 20 tiles of random, junk-bearing, masked content: what meets a tile
 boundary there is proved in tests/test_lib_fuzz_inputs.py, planted wrong rules included.
 
+The `map_reads` stage (the thirteenth, last: the twelve before it draw what they drew).  k of MAP_KS, (w, order), a pre-step of the
+bit-canonical path and one value per parameter of SeedIndex.match, AnchorChains.run, ChainMappings.run and ChainAlignments.run are drawn
+before the sequences (`draw_map_extra`).  `ref_records` are one to four records of a genome with a tandem repeat, a dispersed family on
+both strands, N runs and lower case; `records` are the reads (`make_map_case` lists their kinds).  `pipeline_want` computes what the four
+handles of a ReadMapper hold from bytes alone, through `_minimizer_list_model`, `_seed_index_model`, `_chain_model`, `_mapping_model` and
+`_align_model`; `check_map_reads` holds every field and stats word of one ReadMapper per (k, w, order), kept across cases, to it: the
+whole batch, a prefix on the same handles, then the thinned chains (`thinned_input`) as plain device arrays.  Left to the tests that own
+them: refusals, work_mib groups, the 4095 x 4095 segment, grid steps, stream order, 2^28 spans.
+
 Excluded inputs (what a header rules out is not generated for that stage):
   * bytes of the pre-step's "deleted" class inside a record - needletail_amd.h, "Device batch layout: ... no bytes of the pre-step's
     'deleted' class inside a record (the packer, ntk_batch_append, removed them)": none for PRE_NONE, CR / LF for PRE_STRIP_RETURNS,
@@ -59,14 +69,18 @@ import numpy as np
 
 import needletail_amd as nt
 import _abundance_model as A
+import _align_model as AL
+import _chain_model as CH
 import _colors_model as KM
 import _count_model as CM
 import _dbg_model as DM
 import _kmer_sets_model as KS_
+import _mapping_model as MP
 import _mhset_model as SM
 import _minhash_model as M
 import _minimizer_list_model as MM
 import _record_minhash_model as RM
+import _seed_index_model as SI
 import _sketch_model as S
 import _trim_model as T
 from _count_helpers import M64, PATH_PRES, oracle_items, oracle_values, pack, quality_masked, upload
@@ -74,7 +88,8 @@ from _count_helpers import M64, PATH_PRES, oracle_items, oracle_values, pack, qu
 BYTES, BITS, BITS_CANON = nt.PATH_BYTES_CANONICAL, nt.PATH_BITS, nt.PATH_BITS_CANONICAL
 OLD_STAGES = ("count", "count_wide", "minhash", "minhash_wide", "abundance", "trim")
 NEW_STAGES = ("record_minhash", "kmer_sets", "kmer_sets_wide", "dbg", "colors", "minimizer_list")
-STAGES = OLD_STAGES + NEW_STAGES   # a stage's index seeds its cases: new stages go at the end
+PIPELINE_STAGES = ("map_reads",)
+STAGES = OLD_STAGES + NEW_STAGES + PIPELINE_STAGES   # a stage's index seeds its cases: new stages go at the end
 WIDE_STAGES = ("count_wide", "minhash_wide", "kmer_sets_wide")
 KS = (1, 2, 3, 15, 16, 17, 21, 31, 32)
 WIDE_KS = (33, 34, 47, 48, 49, 62, 63)
@@ -104,7 +119,7 @@ ML_ORDERS = (MM.LEX, MM.HASH)
 # conditions; the counts are the smallest at which they do (seeds 100..139 were searched per stage)
 SLICES = {"count": (103, 3), "count_wide": (111, 3), "minhash": (134, 8), "minhash_wide": (131, 10), "abundance": (104, 3),
           "trim": (111, 4), "record_minhash": (113, 8), "kmer_sets": (117, 3), "kmer_sets_wide": (133, 2), "dbg": (127, 4),
-          "colors": (130, 4), "minimizer_list": (101, 15)}
+          "colors": (130, 4), "minimizer_list": (101, 15), "map_reads": (123, 5)}
 
 LANE_RUN = S.LANE_RUN            # kLaneRun (ntk_wide_count.hip, ntk_sketch.hip, ntk_wide_walk.hpp): window ends per lane
 LONG_PIECES_BYTES = 2048 * 16    # kLongPieces (ntk_trim.hip) 16-byte pieces: beyond it a record goes to rt_copy_long_kernel
@@ -388,6 +403,8 @@ def _append(c, rng, a, kind, cls, rate):
 
 
 def draw_params(rng, stage):
+    if stage == "map_reads":   # ReadMapper lists the (w, k) minimizers of the bit-canonical path
+        return int(rng.choice(MAP_KS)), BITS_CANON, int(rng.choice(MAP_PRES))
     if stage in WIDE_STAGES:
         return int(rng.choice(WIDE_KS)), BYTES, int(rng.choice(WIDE_PRES))
     if stage == "dbg":
@@ -397,9 +414,12 @@ def draw_params(rng, stage):
     return int(rng.choice(KS)), path, pre
 
 
-def draw_extra(rng, stage) -> dict:
+def draw_extra(rng, stage, k=None) -> dict:
     """What a new stage fixes before its records are made: the sketch rule of a record_minhash case, whose num names edge lengths; the
-    window and the order of a minimizer_list case."""
+    window and the order of a minimizer_list case; the window, the order, the class and every parameter of a map_reads case
+    (`draw_map_extra`, which needs the case's k)."""
+    if stage == "map_reads":
+        return draw_map_extra(rng, k)
     if stage == "minimizer_list":
         names = list(ML_W_CLASSES)
         ws = ML_W_CLASSES[names[int(rng.integers(0, len(names)))]]
@@ -421,6 +441,8 @@ def draw_case(seed, stage, it):
     k, path, pre = draw_params(rng, stage)
     if stage in OLD_STAGES:
         return rng, make_case(rng, k, path, pre)
+    if stage == "map_reads":
+        return rng, make_map_case(rng, k, pre, draw_extra(rng, stage, k))
     return rng, make_case(rng, k, path, pre, stage=stage, extra=draw_extra(rng, stage))
 
 
@@ -431,7 +453,10 @@ def slice_digest(stage) -> str:
     seed, n = SLICES[stage]
     for it in range(1, n + 1):
         _, c = draw_case(seed, stage, it)
-        for part in (c.buf(), c.qual_stream().tobytes(), pack(c.ref_records), repr((c.k, c.path, c.pre, c.cutoff)).encode()):
+        parts = (c.buf(), c.qual_stream().tobytes(), pack(c.ref_records), repr((c.k, c.path, c.pre, c.cutoff)).encode())
+        if stage in PIPELINE_STAGES:   # the drawn parameters are the case as much as its bytes are
+            parts += (repr(sorted(c.extra.items())).encode(),)
+        for part in parts:
             h.update(len(part).to_bytes(8, "little"))
             h.update(part)
     return h.hexdigest()
@@ -1241,10 +1266,456 @@ def check_minimizer_list(sess, case, rng):
     return what
 
 
+# ---- the map_reads stage: seeds, chains, mappings and alignments as ReadMapper hands them on --------------------------------------------
+
+MAP_KS = (11, 15, 16, 17, 21)            # the k of `KS` that leave room for seeds
+MAP_PRES = tuple(p for path, p in PATH_PRES if path == BITS_CANON)
+MAP_COPIES = (3, 4, 6)                   # copies of the dispersed family of a plain case
+MAP_FAMILY_COPIES = (12, 16)             # and of a "repeat family" case: one read gets more than MP_LDS_CHAINS chains
+MAP_FAMILY_W = (5, 11)
+MAP_FAMILY_LEN = 200
+THIN_SIZES = (63, 64, 65, 127, 128, 129)   # n and m of the between parts the thinned chains aim at: the 64-row strips of aln_dp_kernel
+THIN_PER_CLASS = 3                         # chains thinned per class and case: the DP of the host model is what a thinned chain costs
+U32_MAX, I31_MAX = (1 << 32) - 1, (1 << 31) - 1
+
+
+def _pick(rng, values):
+    """One of `values`, whose first is the default: that one four times in ten, else any."""
+    return values[0] if rng.random() < 0.4 else values[int(rng.integers(0, len(values)))]
+
+
+def draw_map_extra(rng, k) -> dict:
+    """What a map_reads case fixes before its sequences: the class, (w, order), the copies of the planted family, and one value per
+    parameter of SeedIndex.match, AnchorChains.run, ChainMappings.run and ChainAlignments.run - the default, both ends of the range the
+    model's check_params accepts, and the values next to the kernels' constants (CH_RING = 512 and the 64-lane strip for h; max_dist and
+    bw of tens of bases, which real gaps equal)."""
+    cls = "repeat_family" if rng.random() < 0.25 else "plain"
+    if cls == "plain":
+        names = list(ML_W_CLASSES)
+        ws = ML_W_CLASSES[names[int(rng.integers(0, len(names)))]]
+        w, copies = int(ws[int(rng.integers(0, len(ws)))]), int(rng.choice(MAP_COPIES))
+    else:
+        w, copies = int(rng.choice(MAP_FAMILY_W)), int(rng.choice(MAP_FAMILY_COPIES))
+    max_dist = _pick(rng, (5000, 1, I31_MAX, 30, 50, 80))
+    bw = _pick(rng, (500, 0, 3, 10, 20, None))
+    e = dict(cls=cls, w=w, order=int(ML_ORDERS[int(rng.integers(0, len(ML_ORDERS)))]), copies=copies,
+             max_occ=_pick(rng, (0, 1, 2, copies - 1, copies)), max_dist=max_dist, bw=max_dist if bw is None else min(bw, max_dist),
+             h=_pick(rng, (64, 1, 2, 63, 65, 512)), min_score=_pick(rng, (40, 1, k, k + 1, U32_MAX)), min_cnt=_pick(rng, (3, 1, 2, U32_MAX)),
+             mask_level=_pick(rng, (0.5, 0.0, 1.0)), pri_ratio=_pick(rng, (0.8, 0.0, 1.0)), best_n=_pick(rng, (5, 0, 1)),
+             a=_pick(rng, (2, 1, 255)), b=_pick(rng, (4, 1, 255)), q=_pick(rng, (4, 0, 255)), e=_pick(rng, (2, 1, 255)),
+             band_pad=_pick(rng, (64, 0, 1, 16)), max_seg=_pick(rng, (2048, 1, 4095, 30, 100)))
+    if cls == "repeat_family":   # every few anchors a chain of their own, and each is kept
+        e["max_dist"] = int(rng.choice((3, 5)))
+        e.update(bw=min(e["bw"], e["max_dist"]), min_cnt=1, min_score=int(rng.choice((1, k))), max_occ=int(rng.choice((0, copies))))
+        if e["pri_ratio"]:       # the tiny chains of the copies tie in score: at 1 a secondary is eligible at exactly the ratio of mp_eligible
+            e["pri_ratio"] = 1.0
+    return e
+
+
+MAP_CALL = ("max_occ", "max_dist", "bw", "h", "min_score", "min_cnt", "mask_level", "pri_ratio", "best_n", "a", "b", "q", "e", "band_pad", "max_seg")
+
+
+def map_kw(case) -> dict:
+    """The keyword arguments of ReadMapper.map_aligned of a case."""
+    return {name: case.extra[name] for name in MAP_CALL}
+
+
+def _revcomp(a):
+    return COMP[a[::-1]]
+
+
+def _edited(rng, a, sub, indel):
+    """`a` with substitutions at rate `sub` and insertions and deletions of 1 .. 3 bases at rate `indel`."""
+    a = a.copy()
+    hit = rng.random(a.size) < sub
+    a[hit] = ACGT[rng.integers(0, 4, int(hit.sum()))]
+    out, at = [], 0
+    for p in np.flatnonzero(rng.random(a.size) < indel).tolist():
+        if p < at:
+            continue
+        out.append(a[at:p])
+        n = int(rng.integers(1, 4))
+        if rng.random() < 0.5:
+            out.append(ACGT[rng.integers(0, 4, n)])
+            at = p
+        else:
+            at = p + n
+    out.append(a[at:])
+    return np.concatenate(out).astype(np.uint8)
+
+
+def _ref_cut(rng, refs, L, r=None, where=None):
+    """(bases, reference, start) of a cut of at most L bases of one reference record: anywhere, at its head or at its tail."""
+    r = int(rng.integers(0, len(refs))) if r is None else r
+    n = refs[r].size
+    L = min(L, n)
+    s = 0 if where == "head" else n - L if where == "tail" else int(rng.integers(0, n - L + 1))
+    return refs[r][s:s + L].copy(), r, s
+
+
+def _without(a, at, n):
+    """`a` without the n bases from `at` on: a deletion of exactly n."""
+    return np.concatenate([a[:at], a[at + n:]])
+
+
+def make_map_case(rng, k, pre, extra) -> Case:
+    """One case of the map_reads stage: `ref_records` are one to four reference records cut from a random genome with a tandem repeat, a
+    dispersed family of diverged copies on both strands, N runs and lower-case stretches planted; `records` are the reads, `kinds` what
+    each was made as, `origins` (reference, start, reverse) of the reads cut from a region nothing was planted in, substitutions only."""
+    c = Case(k, BITS_CANON, pre, "map_reads", extra)
+    w, copies, family = extra["w"], extra["copies"], extra["cls"] == "repeat_family"
+    fam_len = MAP_FAMILY_LEN if family else int(rng.integers(120, 301))
+    n = int(rng.integers(2500, 4501)) + copies * fam_len
+    g = ACGT[rng.integers(0, 4, n)].copy()
+    planted = np.zeros(n, dtype=bool)
+    unit = ACGT[rng.integers(0, 4, int(rng.integers(5, 31)))]
+    t_len = int(rng.integers(100, 251))
+    # Now and then a tandem repeat of 64 copies and what a k-mer takes: a reference position of it then matches 63, 64 or 65 read
+    # positions, so the nearest anchor on a diagonal lies 64 anchors back in the sorted order - a whole wave of the chain recurrence.
+    # (One minimizer per period, w >= 3: at w = 1 or 2 a read of it alone would make tens of thousands of anchors.)
+    long_tandem = not family and w >= 3 and rng.random() < 0.25
+    if long_tandem:
+        unit = ACGT[rng.integers(0, 4, int(rng.integers(3, 7)))]
+        t_len = unit.size * (64 + -(-(k - 1) // unit.size) + 1)
+    t_at = int(rng.integers(0, n - t_len))
+    g[t_at:t_at + t_len] = np.resize(unit, t_len)
+    planted[t_at:t_at + t_len] = True
+    fam, win, fam_at = ACGT[rng.integers(0, 4, fam_len)], n // copies, []
+    for j in range(copies):
+        s = j * win + int(rng.integers(0, win - fam_len + 1))
+        copy = _edited(rng, fam, 0.01 if family else 0.02, 0.0) if j else fam.copy()
+        g[s:s + fam_len] = _revcomp(copy) if rng.random() < 0.5 else copy
+        planted[s:s + fam_len] = True
+        fam_at.append(s)
+    for _ in range(int(rng.integers(1, 4))):
+        ln, s = int(rng.integers(1, 41)), int(rng.integers(0, n - 40))
+        g[s:s + ln] = ord("N")
+        planted[s:s + ln] = True
+    for _ in range(int(rng.integers(1, 4))):
+        ln, s = int(rng.integers(20, 201)), int(rng.integers(0, n - 200))
+        g[s:s + ln] |= 0x20
+    cuts = [0] + sorted(set(rng.integers(1, n, int(rng.integers(0, 4))).tolist())) + [n]
+    refs = [g[a:b] for a, b in zip(cuts, cuts[1:])]
+    c.ref_records = [r.tobytes() for r in refs]
+    ref_of = lambda p: int(np.searchsorted(cuts, p, side="right")) - 1   # noqa: E731
+
+    plan = []   # (kind, bases, origin)
+    add = lambda kind, a, origin=None: plan.append((kind, np.asarray(a, dtype=np.uint8), origin))   # noqa: E731
+    for _ in range(int(rng.integers(8, 13)) // (2 if w <= 2 else 1)):   # (at w = 1 every k-mer is a seed: half as many)
+        add("cut", _edited(rng, _ref_cut(rng, refs, int(1500 * rng.random() ** 3))[0], float(rng.choice((0.0, 0.01, 0.03))), 0.003))
+    for _ in range(3):   # substitutions only, from a region nothing was planted in: the origin is known
+        L = int(rng.integers(150, 401))
+        for _try in range(20):
+            a, r, s = _ref_cut(rng, refs, L)
+            if not planted[cuts[r] + s: cuts[r] + s + a.size].any():
+                add("unique", _edited(rng, a, 0.01, 0.0), (r, s))
+                break
+    add("long", _edited(rng, _ref_cut(rng, refs, int(rng.integers(700, 1501)))[0], 0.005, 0.001))
+    for turn in range(2):   # a stretch at a high substitution rate with two indels, between clean flanks: its path leaves the diagonal
+        a = _ref_cut(rng, refs, int(rng.integers(400, 701)))[0]
+        if a.size > 320:
+            ln = int(rng.integers(60, 201))
+            s = int(rng.integers(60, a.size - ln - 59))
+            mid = _edited(rng, a[s:s + ln], 0.3, 0.0)
+            # a deletion and an insertion of d bases each, 30 apart, in either order: n = m, and the path between them runs d off the
+            # diagonal - on the band's edge where d is band_pad
+            d = extra["band_pad"] if 1 <= extra["band_pad"] <= 16 else int(rng.integers(1, 11))
+            x, y = ln // 2 - 15, ln // 2 + 15
+            ins = ACGT[rng.integers(0, 4, d)]
+            mid = np.concatenate([mid[:x], mid[x + d:y], ins, mid[y:]]) if turn else np.concatenate([mid[:x], ins, mid[x:y], mid[y + d:]])
+            a = np.concatenate([a[:s], mid, a[s + ln:]])
+        add("divergent", a)
+    # one indel longer than max_seg, one of exactly bw and one of bw + 1 (a deletion from the read: dr - dq is the indel)
+    max_seg, bw, max_dist = extra["max_seg"], extra["bw"], extra["max_dist"]
+    for kind, d in (("long_indel", max_seg + 1 + int(rng.integers(0, 3)) if max_seg <= 200 else int(rng.integers(30, 81))),
+                    ("bw_indel", bw if 1 <= bw <= 200 else int(rng.integers(1, 21))), ("bw_indel", bw + 1 if bw <= 200 else int(rng.integers(1, 21)))):
+        a = _ref_cut(rng, refs, 400 + d)[0]
+        add(kind, _without(a, a.size // 2 - d // 2, d) if a.size > d + 100 else a)
+    # destroyed blocks whose flanking anchors lie about max_dist apart: the block and the seed behind it are max_dist - (0 .. w) long
+    for _ in range(2):
+        a = _ref_cut(rng, refs, 600)[0]
+        if 20 <= max_dist <= 300 and a.size == 600:
+            for s in (150, 350):
+                ln = max(max_dist - k - int(rng.integers(0, w + 1)), 1)
+                a[s:s + ln] = COMP[a[s:s + ln]]
+        add("spacer", a)
+    for _ in range(2):   # two references, or two strands of one
+        a, r, _ = _ref_cut(rng, refs, int(rng.integers(100, 401)))
+        b = _ref_cut(rng, refs, int(rng.integers(100, 401)), r=(r + 1) % len(refs))[0]
+        add("chimera", np.concatenate([a, _revcomp(b) if len(refs) == 1 or rng.random() < 0.5 else b]))
+    for _ in range(2):
+        add("foreign", ACGT[rng.integers(0, 4, int(rng.integers(50, 301)))])
+    for where in ("head", "tail", "head", "tail"):
+        add(where, _edited(rng, _ref_cut(rng, refs, int(rng.integers(60, 301)), where=where)[0], 0.01, 0.0))
+    for L in (0, 1, k - 1, k, k + w - 2, k + w - 1, k + w):
+        add("edge", _ref_cut(rng, refs, L)[0])
+    for j in rng.integers(0, copies, 2).tolist():   # a copy of the family with its flanks; the tandem repeat with its flanks
+        s = max(fam_at[j] - int(rng.integers(0, 80)), cuts[ref_of(fam_at[j])])
+        add("family", _edited(rng, g[s:min(s + fam_len + 100, cuts[ref_of(s) + 1])], 0.01, 0.0))
+    s = max(t_at - 60, cuts[ref_of(t_at)])
+    add("tandem", g[s:min(t_at + t_len + 60, cuts[ref_of(s) + 1])].copy())
+    if long_tandem:   # and one copy less of it, without the flank behind
+        add("tandem", g[s:min(t_at + t_len - unit.size, cuts[ref_of(s) + 1])].copy())
+    else:             # one unit less and two units more in the middle: chains that fork off the best one, and fork again
+        a, mid = plan[-1][1], t_at - s + t_len // 2
+        if a.size > mid + unit.size:
+            add("tandem", _without(a, mid, unit.size))
+            add("tandem", np.concatenate([a[:mid], a[mid - 2 * unit.size:mid], a[mid:]]))
+    if family:
+        add("family_x2", np.concatenate([fam, fam[:fam_len // 2]]))   # (a unit and a half: the mapping model is quadratic in a read's chains)
+    junk = junk_bytes(pre)
+    order = rng.permutation(len(plan))
+    c.origins = []
+    for i in order.tolist():
+        kind, a, origin = plan[i]
+        rev = bool(rng.random() < 0.5)
+        if rev:
+            a = _revcomp(a)
+        if kind not in ("unique", "edge") and a.size and rng.random() < 0.3:   # junk, lower case, U for T
+            a = a.copy()
+            m = rng.random(a.size)
+            a[m < 0.1] |= 0x20
+            sel = m > 0.99
+            a[sel] = junk[rng.integers(0, junk.size, int(sel.sum()))]
+            a[(m > 0.97) & (m <= 0.99) & (a == ord("T"))] = ord("U")
+        c.records.append(a.tobytes())
+        c.kinds.append(kind)
+        c.classes.append(None)
+        c.origins.append(None if origin is None else origin + (rev,))
+    for _ in range(2):   # exact duplicates
+        j = int(rng.integers(0, len(c.records)))
+        c.records.append(c.records[j])
+        c.kinds.append("dup")
+        c.classes.append(None)
+        c.origins.append(c.origins[j])
+    return c
+
+
+class Pipeline:
+    """The host truth of one run of ReadMapper.index and .map_aligned, stage by stage (`pipeline_want`)."""
+
+
+def _list_of(buf, off, case):
+    """The minimizer list of a packed batch as the seed index takes it: (offsets, pos, values, span << 1 | strand)."""
+    ent = MM.entries_of(buf, case.k, case.extra["w"], BITS_CANON, case.pre, case.extra["order"])
+    o, pos, values, strand, span = MM.csr(ent, off, len(buf), case.k)
+    return SI.as_list(o, pos, values, (span.astype(np.uint32) << np.uint32(1)) | strand.astype(np.uint32))
+
+
+def map_params(case):
+    """(chain, mapping, alignment) parameters of a case as the three models take them."""
+    e = case.extra
+    return (CH.Params(case.k, e["max_dist"], e["bw"], e["h"], e["min_score"], e["min_cnt"]),
+            MP.Params(case.k, int(round(e["mask_level"] * 1000)), int(round(e["pri_ratio"] * 1000)), e["best_n"], e["min_score"]),
+            AL.Params(case.k, e["a"], e["b"], e["q"], e["e"], e["band_pad"], e["max_seg"], 0))
+
+
+def pipeline_want(case, n_reads=None) -> Pipeline:
+    """What the four handles of a ReadMapper hold after index() of the case's references and map_aligned() of its first `n_reads` reads
+    (None: all), from bytes alone: both minimizer lists from `_minimizer_list_model`, the anchors from `_seed_index_model.match`, the
+    chains from `_chain_model.chain`, the marks from `_mapping_model.run`, the alignments of the reported chains from `_align_model.run`,
+    and each stage's stats.  Cached on the case."""
+    cache = case.__dict__.setdefault("_want", {})
+    if n_reads in cache:
+        return cache[n_reads]
+    p = Pipeline()
+    m = len(case.records) if n_reads is None else n_reads
+    ref_buf, ref_off = pack(case.ref_records), T.offsets(case.ref_records)
+    off = case.offsets()[:m + 1]
+    buf = case.buf()[:int(off[m])]
+    p.refs, p.reads = AL.Batch(np.frombuffer(ref_buf, dtype=np.uint8), ref_off), AL.Batch(np.frombuffer(buf, dtype=np.uint8), off)
+    p.ref_list, p.read_list = _list_of(ref_buf, ref_off, case), _list_of(buf, off, case)
+    p.index = SI.Index(p.ref_list)
+    status, p.seeds, p.n_anchors = SI.match(p.index, p.read_list, case.extra["max_occ"])
+    assert status == SI.OK
+    a_off, ref, rev, rpos, qpos, _ = p.seeds
+    p.anchors = CH.as_anchors(a_off, (ref << np.uint32(1)) | rev.astype(np.uint32), rpos, qpos)
+    p.cp, p.mp, p.ap = map_params(case)
+    p.chains = CH.chain(p.anchors, p.cp)
+    ch = p.chains
+    p.mch = MP.Chains(ch.c_offsets, ch.chain_rows, ch.m_offsets, ch.members, rpos, qpos)
+    p.marks = MP.run(p.mch, p.mp)
+    p.inp = AL.Input(p.refs, p.reads, AL.Chains(*p.mch), p.marks.out)
+    p.aln, p.aligned = AL.run(p.inp, p.ap)
+    p.stats = dict(seeds=SI.stats(p.index, p.read_list, p.n_anchors), chains=CH.stats(p.anchors, p.cp, p.chains),
+                   mappings=MP.stats(p.mch, p.marks), alignments=AL.stats(p.inp, p.ap, p.aln, p.aligned))
+    cache[n_reads] = p
+    return p
+
+
+def thin_classes(n, m):
+    """The classes of THIN_SIZES a between part of n x m meets: ("n", size), ("m", size), and "cross" where n != m lie across 64."""
+    out = [("n", n)] * (n in THIN_SIZES) + [("m", m)] * (m in THIN_SIZES)
+    return out + ["cross"] * (min(n, m) >= 1 and min(n, m) < 64 < max(n, m))
+
+
+def thinned_input(case):
+    """(input, sizes): the second alignment input of a case.  Its chains are the reported chains of the whole run, entry by entry in the
+    order reported, each without the members strictly between one pair (i, j) of its members - first and last are kept, order and
+    dr, dq >= 1 survive - so that members i and j, which lay a few bases apart with minimizers between them, bound one between part of
+    n x m bases.  The pair is found by search over all member pairs of the chain: one whose part (at most max_seg) meets the class of
+    `thin_classes` that the case's earlier chains met least often, and fewer than THIN_PER_CLASS times; a chain without such a pair stays
+    whole.  sizes: (n, m) of the part
+    made, per chain (None: whole).  The anchors are the run's own; the selection is every chain."""
+    p = pipeline_want(case)
+    ch, k, max_seg = p.inp.chains, case.k, case.extra["max_seg"]
+    seen, rows, members, m_offsets, sizes = {}, [], [], [0], []
+    for c in p.marks.out.tolist():
+        m = np.asarray(AL.members_of(ch, c), dtype=np.int64)
+        if m.size < 3:   # nothing lies between its ends
+            rows.append(ch.chain_rows[c].copy())
+            members += m.tolist()
+            m_offsets.append(len(members))
+            sizes.append(None)
+            continue
+        r, q = ch.rpos[m].astype(np.int64), ch.qpos[m].astype(np.int64)
+        if int(ch.chain_rows[c, 2]) & 1:
+            q = -q
+        dr, dq = r[None, :] - r[:, None], q[None, :] - q[:, None]   # [i, j]: from member i to member j
+        m0 = np.minimum(np.minimum(dr, dq), k)
+        n_, m_ = dr - m0, dq - m0
+        ok = (np.arange(m.size)[None, :] > np.arange(m.size)[:, None] + 1) & (np.maximum(n_, m_) <= max_seg)
+        cand = {}
+        for i, j in np.argwhere(ok & (np.isin(n_, THIN_SIZES) | np.isin(m_, THIN_SIZES) | ((np.minimum(n_, m_) >= 1) & (np.minimum(n_, m_) < 64) & (np.maximum(n_, m_) > 64)))).tolist():
+            for cls in thin_classes(int(n_[i, j]), int(m_[i, j])):
+                cand.setdefault(cls, (i, j))
+        row = ch.chain_rows[c].copy()
+        cand = {x: pair for x, pair in cand.items() if seen.get(x, 0) < THIN_PER_CLASS}
+        if cand:
+            cls = min(cand, key=lambda x: (seen.get(x, 0), str(x)))
+            i, j = cand[cls]
+            for x in thin_classes(int(n_[i, j]), int(m_[i, j])):
+                seen[x] = seen.get(x, 0) + 1
+            m = np.concatenate([m[:i + 1], m[j:]])
+            sizes.append((int(n_[i, j]), int(m_[i, j])))
+        else:
+            sizes.append(None)
+        row[1] = m.size
+        rows.append(row)
+        members += m.tolist()
+        m_offsets.append(len(members))
+    c_offsets = np.concatenate([[0], np.cumsum(np.diff(p.marks.out_offsets.astype(np.int64)))]).astype(np.uint64)
+    chains = AL.Chains(c_offsets, np.asarray(rows, dtype=np.uint32).reshape(-1, 8), np.asarray(m_offsets, dtype=np.uint64),
+                       np.asarray(members, dtype=np.uint32), ch.rpos, ch.qpos)
+    return AL.Input(p.refs, p.reads, chains, np.arange(len(rows), dtype=np.uint32)), sizes
+
+
+def thinned_want(case):
+    """(input, sizes, result, chains) of the thinned-chain alignment: `_align_model.run` on the arrays of `thinned_input`.  Cached."""
+    cache = case.__dict__.setdefault("_want", {})
+    if "thin" not in cache:
+        inp, sizes = thinned_input(case)
+        cache["thin"] = (inp, sizes) + _thinned_run(case, inp, sizes)
+    return cache["thin"]
+
+
+def _thinned_run(case, inp, sizes):
+    """`_align_model.run(inp, p)`, entry by entry as it builds its result, but for a chain that stayed whole the model's answer of the
+    pipeline run is taken: the same chain over the same anchors and sequences has the same alignment (tests/test_lib_fuzz_inputs.py
+    holds this shortcut to the plain `run`)."""
+    want, p = pipeline_want(case), map_params(case)[2]
+    rows, scores, g_offsets, cigar, chains, cache = [], [], [0], [], [], {}
+    for s, size in enumerate(sizes):
+        got = want.aligned[s] if size is None else AL.chain(inp, s, p, None, cache)
+        chains.append(got)
+        count = lambda op: sum(n for o, n in got.runs if o == op)   # noqa: E731
+        rows.append([AL.TOO_LONG, 0, 0, 0, 0, 0, 0, 0] if got.too_long else
+                    [AL.ALIGNED, len(got.runs), count(AL.OP_EQ), count(AL.OP_X), count(AL.OP_I), count(AL.OP_D),
+                     sum(1 for o, _ in got.runs if o in (AL.OP_I, AL.OP_D)), 0])
+        scores.append(0 if got.too_long else AL.score_of(got.runs, p))
+        cigar += [n << 4 | op for op, n in got.runs]
+        g_offsets.append(len(cigar))
+    return AL.Result(np.asarray(rows, dtype=np.uint32).reshape(-1, 8), np.asarray(scores, dtype=np.int64), np.asarray(g_offsets, dtype=np.uint64),
+                     np.asarray(cigar, dtype=np.uint32)), chains
+
+
+def draw_map(rng, case) -> dict:
+    """The checker's draw of a map_reads case: the prefix of the reads that is mapped again on the same handles."""
+    return dict(prefix=int(rng.integers(1, len(case.records) // 6 + 1)))   # (the models are what a case costs: a sixth at the most)
+
+
+def _dev_u32(a):
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).reshape(-1).view(np.int32).copy()).cuda()
+    torch.cuda.synchronize()
+    return t
+
+
+def _eq_stats(got, want, names, what):
+    _eq([got[n] for n in names if n != "device_bytes"], [want[n] for n in names if n != "device_bytes"], what + " stats")
+
+
+def _hold_pipeline(rm, p, what):
+    """Every field the four handles read back and every stats word but device_bytes, against `p`: the first unequal stage, field and
+    index goes into the Mismatch."""
+    for stage, handle, names, want, stats_names in (("seeds", rm.seeds, SI.FIELDS, p.seeds, SI.STATS), ("chains", rm.chains, CH.FIELDS, p.chains, CH.STATS),
+                                                    ("mappings", rm.mappings, MP.FIELDS, p.marks, MP.STATS),
+                                                    ("alignments", rm.alignments, AL.FIELDS, p.aln, AL.STATS)):
+        got = handle.read()
+        _eq(len(got), len(names), f"{what} {stage} fields")
+        for name, g, w_ in zip(names, got, want):
+            _eq(g, w_, f"{what} {stage} {name}")
+        _eq_stats(handle.stats(), p.stats[stage], stats_names, f"{what} {stage}")
+
+
+def _hold_returned(got, p, what):
+    """What ReadMapper.map_aligned returns - the structured mappings and the four arrays of the alignments - against `p`."""
+    mappings, rest = got[0], got[1:]
+    out, rows = p.marks.out.astype(np.int64), p.marks.rows
+    _eq(mappings.size, out.size, what + " reported rows")
+    sel = rows[out]
+    _eq(mappings["read"], np.repeat(np.arange(p.marks.out_offsets.size - 1), np.diff(p.marks.out_offsets.astype(np.int64))), what + " read")
+    for name in ("qs", "qe", "rs", "re", "score", "cnt", "mlen", "blen", "mapq"):
+        _eq(mappings[name], sel[:, MP.W[name]], f"{what} {name}")
+    _eq(mappings["ref"], sel[:, MP.W["ref_rev"]] >> 1, what + " ref")
+    _eq(mappings["strand"] == b"-", (sel[:, MP.W["ref_rev"]] & 1) == 1, what + " strand")
+    _eq(mappings["primary"], (sel[:, MP.W["flags"]] & MP.PRIMARY) != 0, what + " primary")
+    for name, g, w_ in zip(AL.FIELDS, rest, p.aln):
+        _eq(g, w_, f"{what} alignments {name}")
+
+
+def check_map_reads(sess, case, rng):
+    """index() and map_aligned() on the ReadMapper the session keeps for (k, w, order) - its six handles hold what the case before left -
+    held field by field to `pipeline_want`; a prefix of the reads on the same handles; then the thinned chains through a ChainAlignments
+    of the session as plain device arrays.  Every upload stays alive until the context is synchronised."""
+    k, pre, e = case.k, case.pre, case.extra
+    d = draw_map(rng, case)
+    what = f"map_reads {e} {d}"
+    rm = sess.handle(("map_reads", "mapper", k, e["w"], e["order"]), lambda: nt.ReadMapper(k, e["w"], e["order"], sess.ctx))
+    al = sess.handle(("map_reads", "aligner"), lambda: nt.ChainAlignments(sess.ctx))
+    ref_buf, buf, off = pack(case.ref_records), case.buf(), case.offsets()
+    r_dev, r_off = upload(ref_buf, fill=ord("A")), _dev_u64(T.offsets(case.ref_records))
+    q_dev, q_off = upload(buf, fill=ord("A")), _dev_u64(off)
+    keep = [r_dev, r_off, q_dev, q_off]
+    rm.index(r_dev, len(ref_buf), r_off, len(case.ref_records), pre)
+    n = len(case.records)
+    got = rm.map_aligned(q_dev, len(buf), q_off, n, pre, **map_kw(case))
+    want = pipeline_want(case)
+    _hold_pipeline(rm, want, what + " whole")
+    _hold_returned(got, want, what + " whole, as map_aligned returns it")
+    m = d["prefix"]   # the bytes after the prefix are readable and are not input
+    got = rm.map_aligned(q_dev, int(off[m]), q_off, m, pre, **map_kw(case))
+    _hold_pipeline(rm, pipeline_want(case, m), what + f" first {m} reads")
+    _hold_returned(got, pipeline_want(case, m), what + f" first {m} reads, as map_aligned returns them")
+    inp, _, t_want, t_chains = thinned_want(case)
+    ch = inp.chains
+    t_dev = [_dev_u64(ch.c_offsets), _dev_u32(ch.chain_rows), _dev_u64(ch.m_offsets), _dev_u32(ch.members), _dev_u32(ch.rpos), _dev_u32(ch.qpos),
+             _dev_u32(inp.sel)]
+    keep += t_dev
+    al.run((r_dev, len(ref_buf), r_off, len(case.ref_records)), (q_dev, len(buf), q_off, n), tuple(t_dev[:4]), tuple(t_dev[4:6]), t_dev[6],
+           **map_params(case)[2]._asdict())
+    for name, g, w_ in zip(AL.FIELDS, al.read(), t_want):
+        _eq(g, w_, f"{what} thinned chains {name}")
+    _eq_stats(al.stats(), AL.stats(inp, map_params(case)[2], t_want, t_chains), AL.STATS, what + " thinned chains")
+    sess.ctx.synchronize()
+    del keep
+    return what
+
+
 CHECKERS = {"count": check_count, "count_wide": check_count, "minhash": check_minhash, "minhash_wide": check_minhash,
             "abundance": check_abundance, "trim": check_trim, "record_minhash": check_record_minhash, "kmer_sets": check_kmer_sets,
             "kmer_sets_wide": check_kmer_sets, "dbg": check_dbg, "colors": check_colors,
-            "minimizer_list": check_minimizer_list}
+            "minimizer_list": check_minimizer_list, "map_reads": check_map_reads}
 
 
 def run_case(sess, seed, stage, it):

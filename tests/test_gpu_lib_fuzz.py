@@ -1,5 +1,6 @@
-"""The fixed slices of the structured differential fuzz of the twelve k-mer libraries (tests/_lib_fuzz.py) on a real MI355X: one test per
-stage and width, each a fixed seed and a fixed number of cases (`_lib_fuzz.SLICES`).  tests/test_lib_fuzz_inputs.py proves without a GPU
+"""The fixed slices of the structured differential fuzz of the sixteen libraries (tests/_lib_fuzz.py: the twelve k-mer libraries, and the
+seed index, the chains, the mappings and the alignments as one pipeline) on a real MI355X: one test per stage and width, thirteen stages,
+each a fixed seed and a fixed number of cases (`_lib_fuzz.SLICES`).  tests/test_lib_fuzz_inputs.py proves without a GPU
 that every slice holds the content kinds, the edge lengths and the two-sided conditions that make it mean something; longer runs go
 through tools/lib_fuzz.py and are recorded under profiles/lib_fuzz/.  Truth is the existing host models; every comparison is exact."""
 import pytest
@@ -69,3 +70,9 @@ def test_colors_and_the_compacted_batch(sess):
 
 def test_minimizer_list(sess):
     F.run_slice(sess, "minimizer_list")
+
+
+def test_map_reads_pipeline(sess):
+    """The thirteenth stage: references indexed and reads mapped and aligned on one ReadMapper per (k, w, order) that outlives its
+    cases, every field and stats word of the four handles against the host models; a prefix on the same handles; thinned chains."""
+    F.run_slice(sess, "map_reads")

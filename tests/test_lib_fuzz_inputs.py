@@ -1,6 +1,8 @@
 """The slices of tests/test_gpu_lib_fuzz.py are not vacuous: proved here without a GPU, from the generator (tests/_lib_fuzz.py) and the
 host models alone, over the exact seeds and case counts the GPU tests use (`_lib_fuzz.SLICES`).  These are conditions, not
-measurements: when one fails, the generator changes, not the condition."""
+measurements: when one fails, the generator changes, not the condition.  Thirteen stages over sixteen libraries: the last, `map_reads`,
+has its conditions in tests/_map_reads_report.py (seeds, chains, mappings and alignments on both sides of their rules, every CIGAR walked
+independently of the model, every planted wrong rule of the four models caught)."""
 import functools
 
 import numpy as np
@@ -39,11 +41,13 @@ def test_the_generator_is_deterministic_and_nothing_is_left_out(stage):
         assert c.cutoff == 0 or 33 <= c.cutoff <= 75
         if stage in F.WIDE_STAGES:
             assert c.k in F.WIDE_KS and c.path == F.BYTES and c.pre in F.WIDE_PRES
+        elif stage in F.PIPELINE_STAGES:   # ReadMapper's lists: the bit-canonical path, the k that leave room for seeds
+            assert c.k in F.MAP_KS and c.path == F.BITS_CANON and c.pre in F.MAP_PRES and c.origins == c2.origins
         elif stage == "dbg":   # odd k on a canonical path
             assert c.k in F.DBG_KS and c.k % 2 == 1 and (c.path, c.pre) in F.PATH_PRES and c.path != F.BITS
         else:
             assert c.k in F.KS and (c.path, c.pre) in F.PATH_PRES
-        assert c.stage == (stage if stage in F.NEW_STAGES else "count") and c.extra == c2.extra
+        assert c.stage == (stage if stage in F.NEW_STAGES + F.PIPELINE_STAGES else "count") and c.extra == c2.extra
 
 
 # SHA-256 of the six first slices (`_lib_fuzz.slice_digest`), taken on the commit before the five newer stages were added: the generator
@@ -66,7 +70,7 @@ def test_the_six_first_slices_are_byte_for_byte_what_they_were(stage):
     assert F.edge_lengths(21, stage) == F.edge_lengths(21) and F.long_classes(stage) == F.LONG_CLASSES
 
 
-@pytest.mark.parametrize("stage", F.STAGES)
+@pytest.mark.parametrize("stage", F.OLD_STAGES + F.NEW_STAGES)   # (the map_reads stage has reads of its own kinds: its section below)
 def test_every_content_kind_and_edge_length_occurs(stage):
     kinds, classes, residues = set(), set(), set()
     one_below = one_above = 0
@@ -432,7 +436,7 @@ def test_the_minimizer_list_tile_is_the_rules():
     assert (e["k+w-2"], e["k+w-1"], e["k+w"], e["k+2w-1"]) == (30, 31, 32, 42)      # no window, one, two, a run of w + 1
     assert (e["T1023"], e["T1024"], e["T1025"]) == (1043, 1044, 1045)                  # ML_TILE - 1, ML_TILE, ML_TILE + 1 window ends
     assert set(e) - set(F.edge_lengths(21)) == {"k+w-2", "k+w-1", "k+w", "k+2w-1", "T1023", "T1024", "T1025"}
-    assert F.long_classes("minimizer_list") == () and F.STAGES[-1] == "minimizer_list" and len(F.STAGES) == 12
+    assert F.long_classes("minimizer_list") == () and F.STAGES[11] == "minimizer_list" and F.STAGES[12:] == F.PIPELINE_STAGES
     for name, ws in F.ML_W_CLASSES.items():
         for w in ws:
             assert (name == "one") == (w == 1) and (name == "power_of_two") == (w > 1 and w & (w - 1) == 0)
@@ -613,3 +617,123 @@ PINNED_NEWER = {"minimizer_list": ("915c437abf63380e3c45f19a0ee185a03e723827a6d2
 def test_the_minimizer_list_slice_is_pinned():
     digest, size = PINNED_NEWER["minimizer_list"]
     assert F.SLICES["minimizer_list"] == size and F.slice_digest("minimizer_list") == digest
+
+
+# ---- the map_reads stage ------------------------------------------------------------------------------------------------------------------
+#
+# Everything below is computed from `_lib_fuzz.pipeline_want` and `thinned_want` - the four host models on the case's bytes - by
+# tests/_map_reads_report.py: no GPU.
+
+import _align_model as AL  # noqa: E402
+import _chain_model as CH  # noqa: E402
+import _map_reads_report as R  # noqa: E402
+import _mapping_model as MP  # noqa: E402
+import _seed_index_model as SI  # noqa: E402
+
+
+@functools.lru_cache(maxsize=None)
+def map_reads_reports():
+    """The report of every case of the slice.  A planted wrong rule that an earlier case has caught is not computed again (one case is
+    what the condition asks for); the excused ones are computed on every case."""
+    caught, out = set(), []
+    excused = {(model, rule) for model, rule, _, _ in R.EXCUSED}
+    for _, c in cases("map_reads"):
+        out.append(R.case_report(c, skip=frozenset(caught)))
+        caught |= {key for key, hit in out[-1]["mutants"].items() if hit and key not in excused}
+    return tuple(out), frozenset(caught)
+
+
+def test_the_map_reads_stage_draws_what_it_says():
+    assert F.STAGES[-1] == "map_reads" and len(F.STAGES) == 13 and F.MAP_KS == (11, 15, 16, 17, 21)
+    assert set(F.MAP_PRES) == {pre for path, pre in F.PATH_PRES if path == F.BITS_CANON} and len(F.MAP_PRES) == 4
+    assert MP.LDS_CHAINS == 512 and CH.RING == 512 and AL.SEG_MAX == 4095
+    kinds, classes, ws, orders, pres, n_refs = set(), set(), set(), set(), set(), set()
+    drawn = {name: set() for name in F.MAP_CALL}
+    for _, c in cases("map_reads"):
+        e = c.extra
+        cp, mp, ap = F.map_params(c)
+        assert CH.check_params(cp) == CH.OK and MP.check_params(mp) == MP.OK and AL.check_params(ap) == AL.OK
+        assert e["h"] in (1, 2, 63, 64, 65, 512) and e["best_n"] in (0, 1, 5) and e["band_pad"] in (0, 1, 16, 64)
+        assert e["max_occ"] in (0, 1, 2, e["copies"] - 1, e["copies"]) and e["mask_level"] in (0.0, 0.5, 1.0) and e["pri_ratio"] in (0.0, 0.8, 1.0)
+        assert set(F.map_kw(c)) == set(F.MAP_CALL) and 1 <= len(c.ref_records) <= 4 and 24 <= len(c.records) <= 64
+        assert e["w"] in {w for ws_ in F.ML_W_CLASSES.values() for w in ws_}
+        if e["cls"] == "repeat_family":
+            assert e["max_dist"] <= 5 and e["min_cnt"] == 1 and e["min_score"] <= c.k and e["copies"] in F.MAP_FAMILY_COPIES
+        lengths = {len(r) for r, kind in zip(c.records, c.kinds) if kind == "edge"}
+        assert lengths == {0, 1, c.k - 1, c.k, c.k + e["w"] - 2, c.k + e["w"] - 1, c.k + e["w"]}
+        assert not any(set(F.DELETED[c.pre]) & set(r) for r in c.records + c.ref_records)   # the excluded byte class
+        assert max(len(r) for r in c.records) <= 1600
+        kinds |= set(c.kinds)
+        classes.add(e["cls"]); ws.add(e["w"]); orders.add(e["order"]); pres.add(c.pre); n_refs.add(len(c.ref_records))
+        for name in F.MAP_CALL:
+            drawn[name].add(e[name])
+        assert 1 <= F.draw_map(_copy(cases("map_reads")[0][0]), c)["prefix"] < len(c.records)
+    assert kinds >= {"cut", "unique", "long", "divergent", "long_indel", "bw_indel", "spacer", "chimera", "foreign", "head", "tail", "edge",
+                     "family", "tandem", "family_x2", "dup"}, kinds
+    assert classes == {"plain", "repeat_family"} and orders == set(F.ML_ORDERS) and len(pres) >= 2 and len(n_refs) >= 2 and len(ws) >= 3
+    # each end of the two fractions and the default; the window at 1, 2 and CH_RING and on both sides of the 64-lane strip's edge
+    # (64, 65; five cases do not also draw 63: the budgeted runs of tools/lib_fuzz.py do)
+    assert 0 in drawn["q"] and {0.0, 0.5, 1.0} <= drawn["mask_level"] and {0.0, 0.8, 1.0} <= drawn["pri_ratio"], drawn
+    assert {1, 2, 64, 65, 512} <= drawn["h"], drawn
+    assert F.draw_extra(F.case_rng(F.SLICES["map_reads"][0], "map_reads", 1), "map_reads", 16)["cls"] in ("plain", "repeat_family")
+
+
+def test_map_reads_slice_meets_its_conditions_and_sees_every_planted_wrong_rule():
+    """Seeds, chains, mappings and alignments each on both sides of their rules; every CIGAR walked independently of the alignment
+    model (`walk_cigars` asserts as it goes); the reads of known origin on their origin; every MUTANTS rule of the four models caught by
+    at least one case, and each excused one by none."""
+    reports, caught = map_reads_reports()
+    r = R.slice_report(reports)
+    assert R.conditions(r) == [], r
+    every = set(R.all_mutants())
+    excused = {(model, rule) for model, rule, _, _ in R.EXCUSED}
+    assert len(every) == len(SI.MUTANTS) + len(CH.MUTANTS) + len(MP.MUTANTS) + len(AL.MUTANTS) == 27
+    assert caught == every - excused and excused < every
+    for model, rule, why, owner in R.EXCUSED:   # an excused rule changes no case of the slice, and a test elsewhere owns it
+        assert r["mutants"][model, rule] == 0 and why and owner
+        assert all((model, rule) in rep["mutants"] for rep in reports)
+
+
+def test_two_cases_of_the_map_reads_slice_share_a_mapper():
+    """The checker keeps one ReadMapper per (k, w, order): handle reuse is only exercised where two cases of the slice have one key.  At
+    least one pair does, and its later case leaves some array of the handles larger and some smaller than the earlier case did."""
+    sizes, seen, pairs = {}, {}, []
+    for it, (_, c) in enumerate(cases("map_reads"), 1):
+        p = F.pipeline_want(c)
+        key = (c.k, c.extra["w"], c.extra["order"])
+        sizes[it] = (len(c.records), int(p.read_list[1].size), p.n_anchors, p.chains.chain_rows.shape[0], p.chains.members.size, p.marks.out.size,
+                     p.aln.cigar.size)
+        if key in seen:
+            pairs.append((seen[key], it))
+        seen[key] = it
+    assert pairs, seen
+    assert any(any(b > a for a, b in zip(sizes[i], sizes[j])) and any(b < a for a, b in zip(sizes[i], sizes[j])) for i, j in pairs), (pairs, sizes)
+
+
+def test_the_thinned_chains_keep_the_ends_and_the_order():
+    for _, c in cases("map_reads"):
+        p = F.pipeline_want(c)
+        inp, sizes, want, chains = F.thinned_want(c)
+        ap = F.map_params(c)[2]
+        plain, plain_chains = AL.run(inp, ap)   # the shortcut of `_thinned_run` is the model's plain run
+        assert all(np.array_equal(x, y) and x.dtype == y.dtype for x, y in zip(want, plain)) and AL.stats(inp, ap, want, chains) == AL.stats(inp, ap, plain, plain_chains)
+        assert AL.verify(inp, ap) == AL.OK and inp.sel.size == p.marks.out.size == len(sizes)
+        for s, (c0, size) in enumerate(zip(p.marks.out.tolist(), sizes)):
+            full, thin = AL.members_of(p.inp.chains, c0), AL.members_of(inp.chains, s)
+            assert thin[0] == full[0] and thin[-1] == full[-1] and [m for m in full if m in set(thin)] == thin
+            assert (len(thin) < len(full)) == (size is not None)
+            if size is not None:   # exactly one between part of the size searched for, at most max_seg: it is aligned
+                parts = [(part[3], part[4]) for part in AL.parts_of(inp, s, ap) if part[0] == "between"]
+                assert size in parts and max(size) <= ap.max_seg and (not chains[s].too_long or p.aligned[s].too_long)
+
+
+PINNED_PIPELINE = {"map_reads": ("1d15849482701c59b551e96212312c84e47070a0445374784e853a9febcdb977", (123, 5))}
+
+
+def test_the_map_reads_slice_is_pinned_and_the_twelve_before_it_did_not_move():
+    digest, size = PINNED_PIPELINE["map_reads"]
+    assert F.SLICES["map_reads"] == size and F.slice_digest("map_reads") == digest
+    assert F.STAGES[:12] == F.OLD_STAGES + F.NEW_STAGES and {**PINNED_SLICES, "minimizer_list": (101, 15)}.items() <= F.SLICES.items()
+    assert F.slice_digest("minimizer_list") == PINNED_NEWER["minimizer_list"][0]
+    rng = F.case_rng(1, "minimizer_list", 1)
+    assert rng.bit_generator.state == np.random.default_rng([1, 11, 1]).bit_generator.state   # a stage's index seeds its cases

@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
-"""Time-budgeted structured differential fuzz of the twelve k-mer libraries (count table, wide count table, HyperLogLog sketch, read
+"""Time-budgeted structured differential fuzz of sixteen libraries in thirteen stages: the twelve k-mer libraries (count table, wide count table, HyperLogLog sketch, read
 abundance, read trimmer and its batch writer, MinHash, per-record MinHash with the sketch set, k-mer set algebra narrow and wide, the
-de Bruijn graph, the coloured index, the minimizer lists) against the host models of tests/ - the generator and the checkers are tests/_lib_fuzz.py, whose
+de Bruijn graph, the coloured index, the minimizer lists) and the read-mapping pipeline (seed index, chains, mappings, alignments: one
+stage, `map_reads`, through ReadMapper) against the host models of tests/ - the generator and the checkers are tests/_lib_fuzz.py, whose
 fixed slices run in the suite (tests/test_gpu_lib_fuzz.py).  Needs a gfx950 device, but for --dump.  --stage takes any of
 `_lib_fuzz.STAGES`: count, count_wide, minhash, minhash_wide, abundance, trim, record_minhash, kmer_sets, kmer_sets_wide, dbg, colors,
-minimizer_list.
+minimizer_list, map_reads.
 
     python tools/lib_fuzz.py --seconds 180 --seed 1 > profiles/lib_fuzz/<name>.log
     python tools/lib_fuzz.py --seed 1 --stage trim --replay-it 17            # the device work of that case alone
     python tools/lib_fuzz.py --seed 1 --stage trim --replay-it 17 --dump case.npz   # its input, without a GPU
     python tools/lib_fuzz.py --seed 1 --stage colors --replay-it 5 --dump case.npz  # (a newer stage's dump also holds what it drew first)
+    python tools/lib_fuzz.py --seed 1 --stage map_reads --replay-it 5 --dump case.npz   # reads, references, every drawn parameter in `extra`
 
 Iteration N runs case N of every chosen stage; each (seed, stage, N) has a random stream of its own, so a replay draws exactly what
 the run drew.  A mismatch prints "MISMATCH seed S it N stage X (k, path, pre, kinds ...)" and the settings the checker drew."""
